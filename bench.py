@@ -11,6 +11,16 @@ bitmaps are combined with one RCCL all-gather over xGMI into the round's
 bitmap.  value = 2^20 x steps / max-over-ranks wall time (strong scaling: the
 round is fixed, more GPUs share it).  0.1 % of the round's signatures are
 corrupted (seeded positions): the assembled bitmap is checked against them.
+
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only what that
+headline needs: it builds the round, settles, warms up, times the K steps,
+checks the bitmap, writes it if `--dump-outputs DIR` is given (DIR/round_valid.npy:
+one float32 0/1 per signature in round order, the bitmap a caller of the timed
+path receives; the inputs are seeded, so two builds can be compared bit for
+bit) and prints the result line with the headline's roofline.  The
+weak-scaling figure, the side legs and the CPU baselines described below are
+measured only with `--full`.
+
 A weak-scaling figure (every rank verifies a whole 2^20 round) is reported
 beside it as `weak_scaling`.
 
@@ -18,7 +28,7 @@ Synthetic data: sk_i = SHA-512("pbft-key" || seed || i)[0:32],
 85-byte envelope "PBFT" || kind || view u64 || seq u64 || Blake2b-512("op-"||seq),
 signatures produced by the product's own GPU signer (pbft_sign_batch).
 
-Rank 0 at N = 1 also reports: the dominant kernels' roofline, the 131k-signature
+Rank 0 reports the dominant kernels' roofline; with --full at N = 1 also: the 131k-signature
 shard an 8-GPU node gives each GPU, the host-buffer (PCIe-inclusive) 2^20 round,
 config #2 (n = 4, 1,024 pipelined requests = 8,192 signatures), p50 of a
 4096-signature round and config #5 streaming, and two CPU baselines on this
@@ -75,6 +85,13 @@ def corrupt(S: np.ndarray, frac: float, seed: int):
     S = S.copy()
     S[idx, rng.integers(0, 31, len(idx))] ^= np.uint8(4)
     return S, idx
+
+
+def dump_outputs(path: str, valid: np.ndarray) -> None:
+    """--dump-outputs: the round's bitmap as the timed path's last step left it, one float32 0/1 per signature in
+    round order (2^20 signatures: 4 MiB)."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "round_valid.npy"), valid.astype(np.float32))
 
 
 def dist_env():
@@ -915,7 +932,9 @@ def single_process_main(args):
     for v in vs:
         assert v.set_keys(pub).all()
     c_abi_multi_round(vs, R, S, key_idx, msg, expect, torch, 3, args.warmup)  # settle
-    value, ms, _ = c_abi_multi_round(vs, R, S, key_idx, msg, expect, torch, args.steps, args.warmup)
+    value, ms, got = c_abi_multi_round(vs, R, S, key_idx, msg, expect, torch, args.steps, args.warmup)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, got)
     print(json.dumps({
         "metric": "Ed25519 verifies/sec per node (1M-signature PBFT rounds)", "value": value, "unit": "verifies/s",
         "n_gpus": G, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms, "higher_is_better": True,
@@ -938,8 +957,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--seqs", type=int, default=SEQS, help="sequence numbers in the round (2 x replicas x seqs sigs)")
     ap.add_argument("--replicas", type=int, default=N_REPLICAS)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="only the headline line (no side legs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure everything else the line reports: sequential / weak-scaling "
+                         "figures, the side legs (shard, latency, config #2 / #3 / #5, replica, e2e, key-set legs) and "
+                         "the CPU baselines.  Off by default: a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the round's bitmap after the last timed step to DIR/round_valid.npy (float32 0/1 per "
+                         "signature, round order)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: no CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: no side legs")
     ap.add_argument("--replica-only", action="store_true",
                     help="diagnosis: the headline, then only the replica legs (r06: where the in-bench leg's time goes)")
     ap.add_argument("--latency-iters", type=int, default=200)
@@ -954,6 +980,10 @@ def main():
     args = ap.parse_args()
     if args.single_process:
         return single_process_main(args)
+    # a plain run measures the headline only; --full (and the --replica-only diagnosis) adds the rest
+    full = args.full or args.replica_only
+    extras_on = full and not args.no_extras
+    cpu_on = full and not args.no_cpu
 
     import torch
     ws, rank, local = dist_env()
@@ -1025,9 +1055,11 @@ def main():
             with torch.cuda.stream(fin_stream if pipe else stream):
                 allgather_bitmap(d_local, ws, d_all)
 
-    def check_round():
+    def check_round(dump=None):
         words = round_bitmap(d_local, n_total, ws, d_all)
         got = bitmap_to_bool(words.cpu().numpy().view(np.uint64), n_total)
+        if dump and rank == 0:  # (written before it is judged: a differing bitmap is the one worth comparing)
+            dump_outputs(dump, got)
         assert (got == expect).all(), f"round bitmap differs from the expected bits at {np.nonzero(got != expect)[0][:8]}"
 
     # Settle: the table builds just ran the GPU flat out; keep launching rounds for --settle-s seconds so that
@@ -1069,17 +1101,19 @@ def main():
         kern_avg = float(np.mean([a.elapsed_time(b) for a, b in evs]))  # pipelined: the comb kernel
     else:
         kern_avg = evs[0][0].elapsed_time(evs[0][1]) / args.steps  # the comb + finish pair
-    if ws > 1 and not per_step and n:
-        kern_avg = time_device(v, stream, d, n, args.steps, torch)[0]  # this rank's launch pairs without the gathers
     if ws > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    check_round()  # the bitmap of the last timed step, assembled from every rank's shard
+    check_round(args.dump_outputs)  # the bitmap of the last timed step, assembled from every rank's shard
+    kern_with_gathers = ws > 1 and not per_step
+    if kern_with_gathers and n and full:  # (a run of its own: K more launch pairs)
+        kern_avg = time_device(v, stream, d, n, args.steps, torch)[0]  # this rank's launch pairs without the gathers
+        kern_with_gathers = False
 
     # the same K rounds without pipelining (labelled figure): kernel, finish and all-gather of a round in order
     seq = None
-    if pipelined and not args.no_extras:
+    if pipelined and extras_on:
         sev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
         for _ in range(2):
             step(pipe=False)
@@ -1104,7 +1138,7 @@ def main():
 
     # weak-scaling figure (labelled, not the headline): every rank verifies the WHOLE round
     weak = None
-    if not args.no_extras:
+    if extras_on:
         dw = to_device(torch, dev, R, S, key_idx, msg) if ws > 1 else d
         wb = torch.zeros((n_total + 63) // 64, dtype=torch.int64, device=dev)
         dw["B"] = wb
@@ -1133,7 +1167,7 @@ def main():
         assert (got == expect).all()
 
     extras = {}
-    if rank == 0 and not args.no_extras and ws == 1:
+    if rank == 0 and extras_on and ws == 1:
         # the per-GPU shard of an 8-GPU node (131,072 signatures): kernel time with the finish width it selects
         n8 = shard_bounds(n_total, 0, 8)[1]
         # (warm first: the shard's comb variant -- 8-wave blocks, paired priorities -- is not the 2^20 round's, and
@@ -1193,8 +1227,8 @@ def main():
         extras["e2e_2^20"] = e2e_host_round(v, R, S, key_idx, msg, expect, torch)
         extras["e2e_votes_2^20"] = e2e_votes_round(v, R, S, key_idx, msg, expect, torch)
         extras["votes_device_2^20"] = votes_device_round(v, d, msg, expect, stream, torch, dev)
-        extras["config2"] = config2_leg(v, torch, dev, stream, cpu=not args.no_cpu)
-        extras["config3"] = config3_leg(v, torch, dev, stream, cpu=not args.no_cpu)
+        extras["config2"] = config2_leg(v, torch, dev, stream, cpu=cpu_on)
+        extras["config3"] = config3_leg(v, torch, dev, stream, cpu=cpu_on)
         extras["shuffled_2^20"] = shuffled_leg(v, d, n, stream, torch, dev, expect)
         # the C ABI's single-process multi-GPU form on this process's one GPU (a 1-rank RCCL communicator): its
         # bitmap must equal the headline path's; unmeasured on 8 GPUs in this pipeline
@@ -1217,7 +1251,7 @@ def main():
         # else the comb + finish pair
         ppv = products_comb(pb, pa) if pipelined else products_per_verify(pb, pa)
         products = ppv * n / (kern_avg * 1e-3)
-        cpu = {} if args.no_cpu or ws > 1 else cpu_baselines(pub, R, S, key_idx, msg, expect)
+        cpu = cpu_baselines(pub, R, S, key_idx, msg, expect) if cpu_on and ws == 1 else {}
         pmc = pmc_traffic(pb, pa, n)
         line = {
             "metric": "Ed25519 verifies/sec per node (1M-signature PBFT rounds)",
@@ -1250,9 +1284,12 @@ def main():
                          "gather_bytes_algorithmic": (gather_bytes_per_verify(pb, pa) + INPUT_BYTES) * n,
                          "kernel": (f"comb_kernel<85, plan PA={pa}> (PB={pb}) over this rank's shard (HIP events on "
                                     f"its stream; the finish runs on the second stream)") if pipelined else
-                                   f"comb_kernel<85, plan PA={pa}> (PB={pb}) + finish over this rank's shard",
+                                   f"comb_kernel<85, plan PA={pa}> (PB={pb}) + finish over this rank's shard" +
+                                   (" (the timed region: its all-gathers included; --full times the launch pairs "
+                                    "alone)" if kern_with_gathers else ""),
                          "kernel_avg_ms": kern_avg, "products_per_verify": ppv},
             "pipelined": pipelined,
+            "full": full,
             "sequential_rounds": seq,
             "weak_scaling": weak,
             "cpu_baseline": cpu.get("port"),

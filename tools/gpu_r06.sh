@@ -12,7 +12,7 @@ for s in $STEPS; do
     gputests) timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread > $D/gpu_tests.log 2>&1 ;;
     ingress) timeout -k 10 480 python -u tools/ingress_probe.py > $D/ingress.json 2> $D/ingress.err ;;
     finstamps) echo "finstamps: build/ab variants are gpurun-ignored since r06 (rebuild with tools/build_variant.sh and drop ./build/ab from .gpurunignore)"; false ;;
-    bench) timeout -k 10 600 python -u bench.py > $D/bench.json 2> $D/bench.err ;;
+    bench) timeout -k 10 600 python -u bench.py --full >$D/bench.json 2> $D/bench.err ;;
     finvar) timeout -k 10 400 python -u tools/ab.py build/ab/libpbft_finbase.so build/ab/libpbft_finpre.so build/ab/libpbft_findpp.so build/ab/libpbft_finpar.so build/ab/libpbft_finboth.so --replicas 16 --seqs 32768 --sizes 131072,1048576 --rounds 8 --iters 20 > $D/finvar.txt 2>&1 ;;
     step) timeout -k 10 120 tools/microbench/step_study > $D/step_study.txt 2>&1 ;;
     hostinfo) { nproc; cat /sys/fs/cgroup/cpu.max; python -c "import os; print(len(os.sched_getaffinity(0)))"; grep -m1 "model name" /proc/cpuinfo; for n in /sys/devices/system/node/node*; do echo "$n $(cat $n/cpulist)"; grep -E "MemTotal|MemFree" $n/meminfo; done; cat /sys/class/drm/card*/device/numa_node 2>/dev/null | head -3; cat /sys/kernel/mm/transparent_hugepage/enabled; cat /proc/sys/kernel/numa_balancing; } > $D/hostinfo.txt 2>&1; true ;;
@@ -24,7 +24,7 @@ for s in $STEPS; do
     dppab) timeout -k 10 400 python -u tools/ab.py build/ab/libpbft_finbase.so build/ab/libpbft_findpp.so --replicas 16 --seqs 32768 --sizes 131072 --rounds 24 --iters 20 > $D/dppab.txt 2>&1 ;;
     timeline) timeout -k 10 300 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $D/tl -o tl -- python3 tools/ingress_probe.py --skip-ingress-leg --rounds 4 > $D/timeline.out 2>&1 ;;
     pieceab) timeout -k 10 400 python -u tools/ingress_probe.py --skip-ingress-leg --rounds 40 --flush-ab PBFT_MANY_PIECE=131072,262144 > $D/pieceab.json 2> $D/pieceab.err ;;
-    benchprof) timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $D/benchprof -o bench -- python3 bench.py > $D/benchprof.json 2> $D/benchprof.err && rm -f $D/benchprof/bench_kernel_trace.csv ;;
+    benchprof) timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $D/benchprof -o bench -- python3 bench.py --full >$D/benchprof.json 2> $D/benchprof.err && rm -f $D/benchprof/bench_kernel_trace.csv ;;
     heat) timeout -k 10 300 python -u tools/replica_heat_probe.py > $D/heat.json 2> $D/heat.err ;;
     replonly) timeout -k 10 300 python -u bench.py --replica-only --no-cpu > $D/replonly.json 2> $D/replonly.err ;;
     pfab) timeout -k 10 400 python -u tools/ingress_probe.py --skip-ingress-leg --rounds 40 --flush-ab PBFT_APPLY_PREFETCH=1,2,4,0 > $D/pfab.json 2> $D/pfab.err ;;
