@@ -282,6 +282,44 @@ int pbft_verify_votes_device(pbft_ctx *ctx, const uint8_t *d_R, const uint8_t *d
                              const uint32_t *d_env_idx, const uint8_t *d_envelopes, uint32_t n_env, uint64_t N,
                              uint64_t *d_bitmap, void *stream);
 
+/* Vote tally: the step from the bitmap to a quorum.  Every form above answers per signature; the reference asks per
+ * envelope -- Pbft::prepared / committed_local (src/behavior.rs:177-182, :214-223) count the Prepares / Commits the
+ * log holds for one (view, seq, digest), which State::insert_prepare / insert_commit (src/state.rs:49-67) file per
+ * sender.  pbft_tally_device reduces (bitmap, key_idx, env_idx) of N rows to one signer set and one distinct-signer
+ * count per envelope, with W = ceil(n_signers / 64) words per envelope: bit (k % 64) of d_signers[e * W + k / 64] is 1
+ * iff some row i < N has bitmap bit i set, env_idx[i] == e < n_env and key_idx[i] == k < n_signers; d_count[e] is the
+ * popcount of row e (a signer voting twice under one envelope counts once; the caller compares it with 2f or 2f + 1).
+ * A row whose env_idx >= n_env or key_idx >= n_signers contributes nothing whatever its bit says (the kernel checks
+ * both before it addresses the sets, so any bitmap is safe); bits >= n_signers of a row's last word stay 0.
+ * key_idx and env_idx are read with a byte stride each: separate columns (2, 4) or the votes rows in place
+ * (d_rows + PBFT_VOTES_ROW_KEY, d_rows + PBFT_VOTES_ROW_ENV, both strides PBFT_VOTES_ROW_BYTES).  n_signers is
+ * explicit, so no key set is needed.  Enqueue only, on `stream` (NULL = the context's) -- the stream that produced
+ * d_bitmap, or one ordered after it: a kernel that zeroes the sets (unless accumulating), the tally kernel (lanes that
+ * share a word merge inside their wave, one 8-byte atomic OR per merged group) and the count kernel.  No allocation,
+ * no memset or copy node and no host synchronisation: capturable into a hipGraph as a chain of kernel nodes.  Every pointer is a device pointer on ctx's device, naturally
+ * aligned.  PBFT_EINVAL: unknown flag bits, n_signers 0 or > 65535, key_stride < 2 or odd, env_stride < 4 or not a
+ * multiple of 4, a null input with N > 0, a null output with n_env > 0.  N = 0 zeroes the sets (unless accumulating)
+ * and recomputes the counts; n_env = 0 writes nothing.
+ * PBFT_TALLY_ACCUMULATE: OR into the sets d_signers already holds instead of zeroing them first (OR is idempotent):
+ * the pieces or chunks of one batch, successive pipelined batches or several GPUs' shards of one round fold into one
+ * set, each call with its own rows and its own bitmap words (a piece that starts at row m, a multiple of 64, passes
+ * d_bitmap + m / 64).  d_count is always recomputed from the sets. */
+#define PBFT_TALLY_ACCUMULATE 1u  /* flags: OR into the existing sets instead of zeroing them first */
+int pbft_tally_device(pbft_ctx *ctx, const uint64_t *d_bitmap,
+                      const uint16_t *d_key_idx, uint32_t key_stride,
+                      const uint32_t *d_env_idx, uint32_t env_stride,
+                      uint64_t N, uint32_t n_env, uint32_t n_signers, uint32_t flags,
+                      uint64_t *d_signers /* [n_env][W] */, uint32_t *d_count /* [n_env] */,
+                      void *stream /* NULL = the context's */);
+/* pbft_verify_votes plus the tally of its result; blocking, host buffers.  n_signers is the installed key count
+ * (PBFT_ENOKEYS without a key set): signers_out has n_env * ceil(n_keys / 64) words, count_out n_env entries.
+ * bitmap_out is what pbft_verify_votes writes for the same input.  Runs that function's chunk schedule; each chunk is
+ * tallied on the GPU behind its own kernels, while its columns are in the device staging, into one set (as with
+ * PBFT_TALLY_ACCUMULATE), and the counts follow the last chunk.  PBFT_EBUSY while an async batch is in flight. */
+int pbft_verify_votes_tally(pbft_ctx *ctx, const uint8_t *R, const uint8_t *S, const uint16_t *key_idx,
+                            const uint32_t *env_idx, const uint8_t *envelopes, uint32_t n_env, uint64_t N,
+                            uint64_t *bitmap_out, uint64_t *signers_out, uint32_t *count_out);
+
 /* Pre-size the verify workspace (~230 bytes of HBM per signature) for batches
  * of up to max_n signatures, so that later launches allocate nothing (required
  * before capturing pbft_verify_batch_device into a hipGraph). */

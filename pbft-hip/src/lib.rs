@@ -148,6 +148,40 @@ impl Bitmap {
     }
 }
 
+/// Per-envelope result of a votes batch (pbft_verify_votes_tally): which replicas have a valid vote under each
+/// envelope, and how many.  What Pbft::prepared / committed_local (src/behavior.rs:177-182, :214-223) count.
+#[derive(Clone, Debug, Default, PartialEq, Eq)]
+pub struct Tally {
+    /// `[n_env][words_per_env]`: bit (k % 64) of word k / 64 of envelope e's row = replica k voted validly for e.
+    pub signers: Vec<u64>,
+    /// Distinct valid signers per envelope.
+    pub counts: Vec<u32>,
+    pub words_per_env: usize,
+}
+
+impl Tally {
+    /// At least `need` distinct replicas signed envelope `env` (2f for prepared, 2f + 1 for committed-local).
+    pub fn has_quorum(&self, env: usize, need: u32) -> bool {
+        self.counts.get(env).map_or(false, |&c| c >= need)
+    }
+    /// The replica indices with a valid vote under envelope `env`, ascending.
+    pub fn signers_of(&self, env: usize) -> Vec<u16> {
+        let mut out = Vec::new();
+        if env >= self.counts.len() {
+            return out;
+        }
+        let row = &self.signers[env * self.words_per_env..(env + 1) * self.words_per_env];
+        for (w, &word) in row.iter().enumerate() {
+            let mut m = word;
+            while m != 0 {
+                out.push((w * 64 + m.trailing_zeros() as usize) as u16);
+                m &= m - 1;
+            }
+        }
+        out
+    }
+}
+
 /// Handle of one submitted batch.
 #[derive(Debug, PartialEq, Eq)]
 pub struct Ticket(pub u64);
@@ -207,6 +241,28 @@ impl GpuVerifier {
         self.next += 1;
         self.inflight = Some((self.next, out));
         Ok(Ticket(self.next))
+    }
+    /// Blocking votes-form verify with the per-envelope tally of its result over the installed keys
+    /// (pbft_verify_votes_tally): the bitmap `submit_votes` would give, and who signed each envelope.
+    pub fn verify_votes_tally(&mut self, batch: &VotesBatch) -> Result<(Bitmap, Tally)> {
+        if self.inflight.is_some() {
+            return Err(Error { code: ffi::PBFT_EBUSY, message: "one batch in flight per context".into() });
+        }
+        batch.check_columns()?;
+        let (mut wb, mut wa, mut n_keys) = (0u32, 0u32, 0u32);
+        check(unsafe { ffi::pbft_verify_ctx_info(self.ctx, &mut wb, &mut wa, &mut n_keys) })?;
+        let n = batch.len();
+        let n_env = batch.envelopes.len();
+        let words_per_env = (n_keys as usize + 63) / 64;
+        let mut out = Bitmap::zeros(n);
+        let mut tally = Tally { signers: vec![0u64; n_env * words_per_env], counts: vec![0u32; n_env], words_per_env };
+        check(unsafe {
+            ffi::pbft_verify_votes_tally(self.ctx, batch.r.as_ptr() as *const u8, batch.s.as_ptr() as *const u8,
+                                         batch.key_idx.as_ptr(), batch.env_idx.as_ptr(),
+                                         batch.envelopes.as_ptr() as *const u8, n_env as u32, n as u64,
+                                         out.0.as_mut_ptr(), tally.signers.as_mut_ptr(), tally.counts.as_mut_ptr())
+        })?;
+        Ok((out, tally))
     }
     /// Another context on the same GPU sharing this one's tables (own HIP stream).
     pub fn try_clone(&self) -> Result<Self> {

@@ -5,6 +5,8 @@ include/pbft_verify.h).  This package is the thin host-side binding used by
 tests and bench.py; it never computes a signature check itself.
 """
 from ._lib import EXPORTS, LIB_PATH, PbftError, load  # noqa: F401
-from .verifier import GpuBatchVerifier, MultiGpu, SigBatch, bitmap_to_bool, verify_multi  # noqa: F401
+from .verifier import (TALLY_ACCUMULATE, GpuBatchVerifier, MultiGpu, SigBatch, bitmap_to_bool,  # noqa: F401
+                       quorum, tally_reference, verify_multi)
 
-__all__ = ["GpuBatchVerifier", "MultiGpu", "SigBatch", "bitmap_to_bool", "verify_multi", "PbftError", "load", "LIB_PATH", "EXPORTS"]
+__all__ = ["GpuBatchVerifier", "MultiGpu", "SigBatch", "bitmap_to_bool", "verify_multi", "tally_reference", "quorum",
+           "TALLY_ACCUMULATE", "PbftError", "load", "LIB_PATH", "EXPORTS"]

@@ -22,6 +22,7 @@ EXPORTS = (
     "pbft_verify_set_option", "pbft_verify_batch_device_pipelined", "pbft_verify_votes", "pbft_verify_votes_device",
     "pbft_verify_votes_async", "pbft_verify_votes_stage", "pbft_verify_votes_submit",
     "pbft_multi_create", "pbft_multi_destroy", "pbft_verify_batch_device_multi", "pbft_multi_sync",
+    "pbft_tally_device", "pbft_verify_votes_tally",
     # include/pbft_wire.h
     "pbft_uvi_encode", "pbft_uvi_decode", "pbft_wire_encode_json", "pbft_wire_encode_frame",
     "pbft_wire_decode_json", "pbft_wire_decode_votes", "pbft_records_pack", "pbft_verify_records_device",
@@ -114,6 +115,8 @@ def load() -> ctypes.CDLL:
         "pbft_verify_key_set_id": (i32, [vp, ctypes.POINTER(u64)]),
         "pbft_verify_records_device": (i32, [vp, vp, u64, vp, vp]),
         "pbft_verify_records": (i32, [vp, vp, u64, vp]),
+        "pbft_tally_device": (i32, [vp, vp, vp, u32, vp, u32, u64, u32, u32, u32, vp, vp, vp]),
+        "pbft_verify_votes_tally": (i32, [vp, vp, vp, vp, vp, vp, u32, u64, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -32,6 +32,7 @@
 
 using namespace pbft;
 #include "verify_kernels.h"
+#include "tally_kernels.h"
 // Finish configuration by batch size (signatures per lane, product tree, waves per SIMD), measured on MI355X
 // with the lane-parallel wave inversion (profiles/r03/ab_finish.txt): 131k 0.2115 -> 0.1906 ms (width 2),
 // 262k 0.3628 -> 0.3429 (width 4), 2^20 finish kernel 118.6 -> 91.4 us (width 8, tree, 2 waves per SIMD).
@@ -227,6 +228,11 @@ struct pbft_ctx {
   bool v_short_tail = false;        // the batch's schedule ends with a VOTES_TAIL-row chunk (votes_chunk_end)
   uint64_t rows_out = 0;            // rows whose bitmap words are in the caller's bitmap
   uint64_t chunk_out = 0;           // chunks whose bitmap words are in the caller's bitmap
+  // pbft_verify_votes_tally: signer sets [n_env][W] then counts [n_env] of the batch (grow-only); t_signers is set
+  // only while that call launches its chunks (votes_chunk then tallies each chunk's rows), null otherwise
+  uint64_t* d_tally = nullptr;
+  size_t tally_cap = 0;  // bytes
+  uint64_t* t_signers = nullptr;
 };
 
 #ifndef PBFT_ENV_SCHED
@@ -839,6 +845,12 @@ static int votes_chunk(pbft_ctx* c, const uint8_t* R, const uint8_t* S, const ui
                                    (const uint32_t*)(base + (rows_form ? PBFT_VOTES_ROW_ENV : L.offI)), c->v_env,
                                    c->v_wk, mis, slot));
   if (rc) return rc;
+  // pbft_verify_votes_tally: the chunk's rows join the batch's signer sets while its columns are still in the
+  // staging buffer (lo is a multiple of 64: the chunk's bitmap words are its own)
+  if (c->t_signers)
+    LT("tally", HIP_TRY(launch_tally(c->d_bitmap + lo / 64, base + (rows_form ? PBFT_VOTES_ROW_KEY : L.offK), ks,
+                                     base + (rows_form ? PBFT_VOTES_ROW_ENV : L.offI), 4 * mis, n, c->v_env,
+                                     c->n_keys, c->t_signers, st)));
   LT("rec_consumed", HIP_TRY(hipEventRecord(c->ev_consumed[b], st)));
   if (c->v_readback) {  // this chunk's bitmap words (a few KB) back on their own, for the caller to apply early
     LT("export_bitmap", HIP_TRY(export_words(c, lo / 64, (n + 63) / 64, st)));
@@ -997,6 +1009,7 @@ int pbft_verify_ctx_destroy(pbft_ctx* c) {
   release_base_table(c->device);
   c->adopt(nullptr);
   (void)hipFree(c->d_stage); (void)hipFree(c->d_bitmap); (void)hipFree(c->d_work); (void)hipFree(c->d_wk);
+  (void)hipFree(c->d_tally);
   if (c->h_bitmap) (void)hipHostFree(c->h_bitmap);
   if (c->h_stage) (void)hipHostFree(c->h_stage);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -1875,6 +1888,78 @@ int pbft_verify_votes_device(pbft_ctx* c, const uint8_t* dR, const uint8_t* dS, 
   if (rc) return rc;
   return launch_verify(c, dR, dS, dK, d_envelopes, PBFT_ENVELOPE_LEN, PBFT_ENVELOPE_LEN, N, dB, st, 32, 2, nullptr,
                        d_env_idx, n_env, dWK);
+}
+
+// ---- vote tally (include/pbft_verify.h; kernels: tally.hip) ----
+// Three launches (two when accumulating) on the caller's stream: no allocation, no synchronisation.
+int pbft_tally_device(pbft_ctx* c, const uint64_t* dB, const uint16_t* dK, uint32_t key_stride, const uint32_t* dI,
+                      uint32_t env_stride, uint64_t N, uint32_t n_env, uint32_t n_signers, uint32_t flags,
+                      uint64_t* d_signers, uint32_t* d_count, void* stream) {
+  if (!c) return set_err(PBFT_EINVAL, "null context");
+  if (flags & ~PBFT_TALLY_ACCUMULATE) return set_err(PBFT_EINVAL, "unknown tally flags");
+  if (n_signers == 0 || n_signers > 65535) return set_err(PBFT_EINVAL, "n_signers out of range");
+  if (key_stride < 2 || (key_stride & 1) || env_stride < 4 || (env_stride & 3))
+    return set_err(PBFT_EINVAL, "bad tally strides");
+  if (N && (!dB || !dK || !dI)) return set_err(PBFT_EINVAL, "null tally input");
+  if (n_env && (!d_signers || !d_count)) return set_err(PBFT_EINVAL, "null tally output");
+  if (((uintptr_t)dB & 7) || ((uintptr_t)dK & 1) || ((uintptr_t)dI & 3) || ((uintptr_t)d_signers & 7) ||
+      ((uintptr_t)d_count & 3))
+    return set_err(PBFT_EINVAL, "misaligned tally pointer");
+  if ((N + TALLY_BLOCK - 1) / TALLY_BLOCK > 0x7fffffffull) return set_err(PBFT_EINVAL, "N too large for one launch");
+  if (n_env == 0) return PBFT_OK;  // nothing to write
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  if (!(flags & PBFT_TALLY_ACCUMULATE)) HIP_TRY(launch_tally_zero(d_signers, n_env, n_signers, st));
+  if (N)
+    HIP_TRY(launch_tally(dB, (const uint8_t*)dK, key_stride, (const uint8_t*)dI, env_stride, N, n_env, n_signers,
+                         d_signers, st));
+  HIP_TRY(launch_tally_count(d_signers, n_env, n_signers, d_count, st));
+  return PBFT_OK;
+}
+
+// pbft_verify_votes with every chunk tallied on its own stream while its columns are resident (the staging keeps
+// VOTES_BUFS chunks, a batch may have more), all into one zeroed set -- OR is idempotent, so the chunks fold like
+// PBFT_TALLY_ACCUMULATE pieces; then the counts and the copies back on the context stream, which follows both.
+int pbft_verify_votes_tally(pbft_ctx* c, const uint8_t* R, const uint8_t* S, const uint16_t* K,
+                            const uint32_t* env_idx, const uint8_t* envelopes, uint32_t n_env, uint64_t N,
+                            uint64_t* out, uint64_t* signers_out, uint32_t* count_out) {
+  if (!c) return set_err(PBFT_EINVAL, "null context");
+  if (c->in_flight) return set_err(PBFT_EBUSY, "async batch in flight");
+  if (N && (!R || !S || !K || !env_idx || !out || !envelopes || n_env == 0))
+    return set_err(PBFT_EINVAL, "bad votes arguments");
+  if (c->n_keys == 0) return set_err(PBFT_ENOKEYS, "pbft_verify_set_keys not called");
+  if (n_env && (!signers_out || !count_out)) return set_err(PBFT_EINVAL, "null tally output");
+  if (n_env == 0) return PBFT_OK;
+  const size_t set_bytes = (size_t)n_env * tally_words(c->n_keys) * 8, cnt_bytes = (size_t)n_env * 4;
+  if (N == 0) {
+    memset(signers_out, 0, set_bytes);
+    memset(count_out, 0, cnt_bytes);
+    return PBFT_OK;
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  if (set_bytes + cnt_bytes > c->tally_cap) {
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->d_tally) HIP_TRY(hipFree(c->d_tally));
+    c->d_tally = nullptr;
+    c->tally_cap = 0;
+    if (hipMalloc(&c->d_tally, set_bytes + cnt_bytes) != hipSuccess) return set_err(PBFT_ENOMEM, "tally alloc");
+    c->tally_cap = set_bytes + cnt_bytes;
+  }
+  // zeroed on the context stream ahead of the batch: stream2's chunks wait for the envelope schedule behind it
+  HIP_TRY(launch_tally_zero(c->d_tally, n_env, c->n_keys, c->stream));
+  c->t_signers = c->d_tally;
+  int rc = pbft_verify_votes_async(c, R, S, K, env_idx, envelopes, n_env, N, out);
+  c->t_signers = nullptr;
+  if (rc) return rc;
+  uint32_t* d_count = (uint32_t*)((uint8_t*)c->d_tally + set_bytes);
+  hipError_t e = launch_tally_count(c->d_tally, n_env, c->n_keys, d_count, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(signers_out, c->d_tally, set_bytes, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(count_out, d_count, cnt_bytes, hipMemcpyDeviceToHost, c->stream);
+  rc = pbft_verify_wait(c);  // (the bitmap; also ends the batch when a step above failed)
+  HIP_TRY(e);
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return PBFT_OK;
 }
 
 // Binary wire records (include/pbft_wire.h): R at +0, S at +32, envelope at +64,

@@ -75,6 +75,34 @@ def bitmap_to_bool(bitmap: np.ndarray, n: int) -> np.ndarray:
     return bits[:n].astype(bool)
 
 
+TALLY_ACCUMULATE = 1  # PBFT_TALLY_ACCUMULATE (include/pbft_verify.h)
+
+
+def tally_reference(bits, key_idx, env_idx, n_env: int, n_signers: int):
+    """The semantics of pbft_tally_device in numpy: (signers, counts).  signers is (n_env, W) uint64 with
+    W = ceil(n_signers / 64): bit (k % 64) of signers[e, k // 64] is 1 iff some row i has bits[i] set,
+    env_idx[i] == e < n_env and key_idx[i] == k < n_signers; counts[e] (uint32) is the popcount of row e, so a signer
+    that votes twice under one envelope counts once and a row with either index out of range contributes nothing.
+    bits: bool per row (bitmap_to_bool of the verifier's bitmap)."""
+    bits = np.asarray(bits).astype(bool).reshape(-1)
+    k = np.asarray(key_idx).reshape(-1).astype(np.int64)
+    e = np.asarray(env_idx).reshape(-1).astype(np.int64)
+    if not (len(bits) == len(k) == len(e)):
+        raise ValueError("bits, key_idx and env_idx must have the same length")
+    W = (n_signers + 63) // 64
+    member = np.zeros((n_env, W * 64), dtype=bool)
+    ok = bits & (e < n_env) & (k < n_signers)
+    member[e[ok], k[ok]] = True
+    signers = np.packbits(member, axis=1, bitorder="little").view(np.uint64).reshape(n_env, W)
+    return signers, member.sum(axis=1).astype(np.uint32)
+
+
+def quorum(counts, need: int) -> np.ndarray:
+    """Envelopes with at least `need` distinct valid signers (2f for prepared, 2f + 1 for committed-local:
+    src/behavior.rs:177-182, :214-223); bool per envelope."""
+    return np.asarray(counts) >= need
+
+
 def verify_multi(verifiers, b: "SigBatch") -> np.ndarray:
     """pbft_verify_batch_multi: shard one batch over several contexts (GPUs and/or clones); bitmap words."""
     lib = load()
@@ -280,6 +308,34 @@ class GpuBatchVerifier:
                             n_env: int, n: int, d_bitmap: int, stream: int = 0) -> None:
         check(self._lib.pbft_verify_votes_device(self._ctx, d_R, d_S, d_key_idx, d_env_idx, d_envelopes, n_env, n,
                                                  d_bitmap, stream or None))
+
+    def tally_device(self, d_bitmap: int, d_key_idx: int, d_env_idx: int, n: int, n_env: int, n_signers: int,
+                     d_signers: int, d_count: int, stream: int = 0, key_stride: int = 2, env_stride: int = 4,
+                     flags: int = 0) -> None:
+        """pbft_tally_device: enqueue the tally of n rows (raw device pointers; d_signers is [n_env][W] u64 with
+        W = ceil(n_signers / 64), d_count [n_env] u32) on `stream`, behind the launch that wrote d_bitmap.
+        flags = TALLY_ACCUMULATE ORs into the sets already there."""
+        check(self._lib.pbft_tally_device(self._ctx, d_bitmap or None, d_key_idx or None, key_stride,
+                                          d_env_idx or None, env_stride, n, n_env, n_signers, flags,
+                                          d_signers or None, d_count or None, stream or None))
+
+    def verify_votes_tally(self, R, S, key_idx, env_idx, envelopes):
+        """pbft_verify_votes_tally: verify_votes and the tally of its result over the installed keys; returns
+        (bitmap words, signers (n_env, W) uint64, counts (n_env,) uint32)."""
+        R = np.ascontiguousarray(R, np.uint8).reshape(-1, 32)
+        S = np.ascontiguousarray(S, np.uint8).reshape(-1, 32)
+        K = np.ascontiguousarray(key_idx, np.uint16).reshape(-1)
+        I = np.ascontiguousarray(env_idx, np.uint32).reshape(-1)
+        E = np.ascontiguousarray(envelopes, np.uint8).reshape(-1, 85)
+        n = len(R)
+        if not (len(S) == len(K) == len(I) == n):
+            raise ValueError("R, S, key_idx, env_idx must have the same length")
+        out = np.zeros((n + 63) // 64, dtype=np.uint64)
+        signers = np.zeros((len(E), (self.n_keys + 63) // 64), dtype=np.uint64)
+        counts = np.zeros(len(E), dtype=np.uint32)
+        check(self._lib.pbft_verify_votes_tally(self._ctx, _ptr(R), _ptr(S), _ptr(K), _ptr(I), _ptr(E), len(E), n,
+                                                _ptr(out), _ptr(signers), _ptr(counts)))
+        return out, signers, counts
 
     def verify_records(self, records: np.ndarray) -> np.ndarray:
         """Blocking verify of (N, 160) binary wire records (include/pbft_wire.h); returns bitmap words."""
