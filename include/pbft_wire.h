@@ -128,6 +128,62 @@ int pbft_verify_records_device(pbft_ctx *ctx, const uint8_t *d_records, uint64_t
 /* Same from host records (one H2D copy of N x 160 bytes). Blocking. */
 int pbft_verify_records(pbft_ctx *ctx, const uint8_t *records, uint64_t N, uint64_t *bitmap_out);
 
+/* ---- JSON frames decoded on the device (kernel: pbft_amd/csrc/wire_decode.hip) ----
+ * The canonical form of a signed vote, exactly what serde_json and pbft_wire_encode_json write,
+ *   {"Prepare":{"view":V,"sequence_number":N,"digest":"<128 hex>","replica":R,"signature":"<128 hex>"}}
+ * (or "Commit"; PBFT_FRAME_MIN..PBFT_FRAME_MAX bytes), is parsed by one GPU lane per frame into the 160-byte record
+ * above and a 24-byte head.  Frame f is record f, head f and bit f: no compaction.  Any other frame -- a PrePrepare,
+ * a ClientRequest, whitespace, another field order, an escape, an invalid number or hex digit -- is marked
+ * PBFT_WIRE_EDEFER on the device: the general parser decides about it, with serde's rules (pbft_verify_frames does
+ * that).  The signer of a vote is the connection's authenticated peer, never a frame field: with a peer array,
+ * frame f is PBFT_WIRE_ESIGNER unless its "replica" equals peer[f] (tested on Prepare and Commit only).
+ * A frame whose status is not PBFT_WIRE_OK has an all-zero record with key index 0xFFFF (bit 0 under any key set),
+ * and view = seq = kind = 0, key_idx = 0xFFFF in its head. */
+#define PBFT_WIRE_EDEFER 6 /* not the canonical vote form: pbft_wire_decode_json decides (device form only) */
+#define PBFT_FRAME_MIN 336
+#define PBFT_FRAME_MAX 379
+typedef struct {
+  uint64_t view, seq; /* of an OK frame */
+  uint16_t key_idx;   /* the signer ("replica") of an OK frame */
+  uint8_t kind;       /* PBFT_MSG_* of an OK frame */
+  uint8_t status;     /* PBFT_WIRE_* */
+  uint32_t frame_len; /* the frame's body length as given */
+} pbft_frame_head;
+
+/* Host: the varint scan of a stream of whole frames -> body offset and length of each (the framing loop of
+ * pbft_wire_decode_votes: stops at the first incomplete frame or after max_frames; PBFT_EINVAL on a framing error
+ * at *consumed).  off / flen hold max_frames entries. */
+int pbft_wire_frame_index(const uint8_t *stream, size_t len, uint64_t max_frames, uint64_t *off, uint32_t *flen,
+                          uint64_t *n_frames, uint64_t *consumed);
+
+/* Device, enqueue only (one kernel node: no allocation, copy or synchronisation; capturable): frame f = bytes
+ * [d_off[f], d_off[f] + d_len[f]) of d_stream -> d_records[f], d_heads[f].  d_stream must be 16-byte aligned and
+ * readable up to stream_bytes rounded up to 16 (whole 16-byte granules of that range are read, nothing beyond
+ * it); d_records 16-byte aligned, the others naturally.  A frame that does not lie inside stream_bytes is
+ * PBFT_WIRE_EDEFER and is not read.  d_peer: NULL or one authenticated replica index per frame.
+ * PBFT_EINVAL: null / misaligned pointer, n_replicas 0 or > 65535, N > 2^32. */
+int pbft_wire_decode_frames_device(pbft_ctx *ctx, const uint8_t *d_stream, uint64_t stream_bytes,
+                                   const uint64_t *d_off, const uint32_t *d_len, const uint16_t *d_peer,
+                                   uint32_t n_replicas, uint64_t N, uint8_t *d_records, pbft_frame_head *d_heads,
+                                   void *stream);
+
+/* Device, enqueue only: the decode, then pbft_verify_records_device of d_records on the same stream.  Every frame
+ * that is not PBFT_WIRE_OK (PBFT_WIRE_EDEFER included) has bit 0.  Call pbft_verify_reserve(N) before a capture. */
+int pbft_verify_frames_device(pbft_ctx *ctx, const uint8_t *d_stream, uint64_t stream_bytes, const uint64_t *d_off,
+                              const uint32_t *d_len, const uint16_t *d_peer, uint32_t n_replicas, uint64_t N,
+                              uint8_t *d_records, pbft_frame_head *d_heads, uint64_t *d_bitmap, void *stream);
+
+/* Host, blocking, the complete form: stream and index to the device, decode there, the heads back; every
+ * PBFT_WIRE_EDEFER frame then goes through pbft_wire_decode_json on the host and gets the status
+ * pbft_wire_decode_votes would give it (a signed PrePrepare that passes is a kind-0 record), plus the peer rule; the
+ * records and heads of those that became OK are patched on the device, and all N records are verified.
+ * heads_out[f].status is never PBFT_WIRE_EDEFER.  records_out: NULL or N x 160 bytes.  bitmap_out: ceil(N / 64) words.
+ * PBFT_EINVAL also for a frame with off + flen beyond stream_bytes; PBFT_ENOKEYS / PBFT_EBUSY as
+ * pbft_verify_records. */
+int pbft_verify_frames(pbft_ctx *ctx, const uint8_t *stream, uint64_t stream_bytes, const uint64_t *off,
+                       const uint32_t *flen, const uint16_t *peer, uint32_t n_replicas, uint64_t N,
+                       uint64_t *bitmap_out, pbft_frame_head *heads_out, uint8_t *records_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,6 +32,24 @@ pub struct pbft_votes_staging {
     pub row_stride: u32,
 }
 
+/// Head of one decoded frame (pbft_wire_decode_frames_device / pbft_verify_frames): 24 bytes.  view, seq and kind
+/// are set only when `status` is PBFT_WIRE_OK; key_idx is 0xFFFF otherwise.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct pbft_frame_head {
+    pub view: u64,
+    pub seq: u64,
+    pub key_idx: u16,
+    pub kind: u8,
+    pub status: u8,
+    pub frame_len: u32,
+}
+
+pub const PBFT_WIRE_OK: u8 = 0;
+pub const PBFT_WIRE_EDEFER: u8 = 6;
+pub const PBFT_FRAME_MIN: u32 = 336;
+pub const PBFT_FRAME_MAX: u32 = 379;
+
 pub const PBFT_VOTES_ROW_BYTES: usize = 72;
 pub const PBFT_VOTES_ROW_KEY: usize = 64;
 pub const PBFT_VOTES_ROW_ENV: usize = 68;
@@ -311,4 +329,17 @@ extern "C" {
     pub fn pbft_verify_records_device(ctx: *mut pbft_ctx, d_records: *const u8, n: u64, d_bitmap: *mut u64,
                                       stream: *mut c_void) -> c_int;
     pub fn pbft_verify_records(ctx: *mut pbft_ctx, records: *const u8, n: u64, bitmap_out: *mut u64) -> c_int;
+    pub fn pbft_wire_frame_index(stream: *const u8, len: usize, max_frames: u64, off: *mut u64, flen: *mut u32,
+                                 n_frames: *mut u64, consumed: *mut u64) -> c_int;
+    pub fn pbft_wire_decode_frames_device(ctx: *mut pbft_ctx, d_stream: *const u8, stream_bytes: u64,
+                                          d_off: *const u64, d_len: *const u32, d_peer: *const u16,
+                                          n_replicas: u32, n: u64, d_records: *mut u8,
+                                          d_heads: *mut pbft_frame_head, stream: *mut c_void) -> c_int;
+    pub fn pbft_verify_frames_device(ctx: *mut pbft_ctx, d_stream: *const u8, stream_bytes: u64, d_off: *const u64,
+                                     d_len: *const u32, d_peer: *const u16, n_replicas: u32, n: u64,
+                                     d_records: *mut u8, d_heads: *mut pbft_frame_head, d_bitmap: *mut u64,
+                                     stream: *mut c_void) -> c_int;
+    pub fn pbft_verify_frames(ctx: *mut pbft_ctx, stream: *const u8, stream_bytes: u64, off: *const u64,
+                              flen: *const u32, peer: *const u16, n_replicas: u32, n: u64, bitmap_out: *mut u64,
+                              heads_out: *mut pbft_frame_head, records_out: *mut u8) -> c_int;
 }

@@ -182,6 +182,9 @@ impl Tally {
     }
 }
 
+/// Head of one decoded frame (ffi::pbft_frame_head): status, and view / seq / kind / signer of an OK frame.
+pub type FrameHead = ffi::pbft_frame_head;
+
 /// Handle of one submitted batch.
 #[derive(Debug, PartialEq, Eq)]
 pub struct Ticket(pub u64);
@@ -263,6 +266,34 @@ impl GpuVerifier {
                                          out.0.as_mut_ptr(), tally.signers.as_mut_ptr(), tally.counts.as_mut_ptr())
         })?;
         Ok((out, tally))
+    }
+    /// The whole frames of one connection's byte stream (UviBytes + serde_json, what `upgrade_inbound` reads)
+    /// decoded on the GPU and verified (pbft_wire_frame_index + pbft_verify_frames).  `peer`: the connection's
+    /// authenticated replica index -- a vote naming another replica is PBFT_WIRE_ESIGNER.  Returns the bitmap (bit f:
+    /// frame f is a signed message whose signature verifies), one head per frame with the status
+    /// pbft_wire_decode_votes would give it, and the bytes consumed (an incomplete last frame stays with the caller).
+    pub fn verify_frames(&mut self, stream: &[u8], peer: Option<u16>,
+                         n_replicas: u32) -> Result<(Bitmap, Vec<FrameHead>, usize)> {
+        if self.inflight.is_some() {
+            return Err(Error { code: ffi::PBFT_EBUSY, message: "one batch in flight per context".into() });
+        }
+        let cap = stream.len(); // a frame is at least its one varint byte
+        let (mut off, mut flen) = (vec![0u64; cap], vec![0u32; cap]);
+        let (mut n, mut used) = (0u64, 0u64);
+        check(unsafe {
+            ffi::pbft_wire_frame_index(stream.as_ptr(), stream.len(), cap as u64, off.as_mut_ptr(), flen.as_mut_ptr(),
+                                       &mut n, &mut used)
+        })?;
+        let n = n as usize;
+        let peers = peer.map(|p| vec![p; n]);
+        let mut out = Bitmap::zeros(n);
+        let mut heads = vec![FrameHead::default(); n];
+        check(unsafe {
+            ffi::pbft_verify_frames(self.ctx, stream.as_ptr(), stream.len() as u64, off.as_ptr(), flen.as_ptr(),
+                                    peers.as_ref().map_or(ptr::null(), |p| p.as_ptr()), n_replicas, n as u64,
+                                    out.0.as_mut_ptr(), heads.as_mut_ptr(), ptr::null_mut())
+        })?;
+        Ok((out, heads, used as usize))
     }
     /// Another context on the same GPU sharing this one's tables (own HIP stream).
     pub fn try_clone(&self) -> Result<Self> {

@@ -7,6 +7,7 @@ tests and bench.py; it never computes a signature check itself.
 from ._lib import EXPORTS, LIB_PATH, PbftError, load  # noqa: F401
 from .verifier import (TALLY_ACCUMULATE, GpuBatchVerifier, MultiGpu, SigBatch, bitmap_to_bool,  # noqa: F401
                        quorum, tally_reference, verify_multi)
+from .wire import FrameHead, frame_index  # noqa: F401
 
 __all__ = ["GpuBatchVerifier", "MultiGpu", "SigBatch", "bitmap_to_bool", "verify_multi", "tally_reference", "quorum",
-           "TALLY_ACCUMULATE", "PbftError", "load", "LIB_PATH", "EXPORTS"]
+           "TALLY_ACCUMULATE", "FrameHead", "frame_index", "PbftError", "load", "LIB_PATH", "EXPORTS"]

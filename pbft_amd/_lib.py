@@ -26,7 +26,8 @@ EXPORTS = (
     # include/pbft_wire.h
     "pbft_uvi_encode", "pbft_uvi_decode", "pbft_wire_encode_json", "pbft_wire_encode_frame",
     "pbft_wire_decode_json", "pbft_wire_decode_votes", "pbft_records_pack", "pbft_verify_records_device",
-    "pbft_verify_records", "pbft_wire_encode_votes",
+    "pbft_verify_records", "pbft_wire_encode_votes", "pbft_wire_frame_index", "pbft_wire_decode_frames_device",
+    "pbft_verify_frames_device", "pbft_verify_frames",
 )
 
 ERRORS = {0: "PBFT_OK", -1: "PBFT_EINVAL", -2: "PBFT_EHIP", -3: "PBFT_ENOKEYS",
@@ -117,6 +118,10 @@ def load() -> ctypes.CDLL:
         "pbft_verify_records": (i32, [vp, vp, u64, vp]),
         "pbft_tally_device": (i32, [vp, vp, vp, u32, vp, u32, u64, u32, u32, u32, vp, vp, vp]),
         "pbft_verify_votes_tally": (i32, [vp, vp, vp, vp, vp, vp, u32, u64, vp, vp, vp]),
+        "pbft_wire_frame_index": (i32, [u8p, ctypes.c_size_t, u64, vp, vp, vp, vp]),
+        "pbft_wire_decode_frames_device": (i32, [vp, vp, u64, vp, vp, vp, u32, u64, vp, vp, vp]),
+        "pbft_verify_frames_device": (i32, [vp, vp, u64, vp, vp, vp, u32, u64, vp, vp, vp, vp]),
+        "pbft_verify_frames": (i32, [vp, vp, u64, vp, vp, vp, u32, u64, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

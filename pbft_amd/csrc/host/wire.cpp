@@ -663,6 +663,27 @@ int pbft_wire_decode_votes(const uint8_t* stream, size_t len, uint32_t n_replica
   return 0;
 }
 
+int pbft_wire_frame_index(const uint8_t* stream, size_t len, uint64_t max_frames, uint64_t* off, uint32_t* flen,
+                          uint64_t* n_frames, uint64_t* consumed) {
+  if (!n_frames || !consumed || (!stream && len) || (max_frames && (!off || !flen))) return PBFT_EINVAL;
+  *n_frames = *consumed = 0;
+  size_t at = 0;
+  while (at < len && *n_frames < max_frames) {  // (the framing loop of pbft_wire_decode_votes)
+    uint64_t fl;
+    size_t hn;
+    const int rc = pbft_uvi_decode(stream + at, len - at, &fl, &hn);
+    if (rc == 1) break;
+    if (rc != 0 || fl > PBFT_UVI_MAX_FRAME) return PBFT_EINVAL;
+    if (len - at - hn < fl) break;  // incomplete frame: keep for the next call
+    off[*n_frames] = at + hn;
+    flen[*n_frames] = (uint32_t)fl;
+    ++*n_frames;
+    at += hn + (size_t)fl;
+    *consumed = at;
+  }
+  return 0;
+}
+
 int pbft_wire_encode_votes(uint64_t N, const uint8_t* kind, const uint64_t* view, const uint64_t* seq,
                            const uint8_t* digests, const uint32_t* replica, const uint8_t* sigs, uint8_t* out,
                            size_t cap, size_t* len) {

@@ -27,12 +27,14 @@
 
 #include "../../include/pbft_verify.h"
 #include "../../include/pbft_wire.h"
+#include "../../include/pbft_replica.h"  // pbft_envelope
 #include "digest_kernels.h"
 #include "verify_core.h"
 
 using namespace pbft;
 #include "verify_kernels.h"
 #include "tally_kernels.h"
+#include "wire_decode_kernels.h"
 // Finish configuration by batch size (signatures per lane, product tree, waves per SIMD), measured on MI355X
 // with the lane-parallel wave inversion (profiles/r03/ab_finish.txt): 131k 0.2115 -> 0.1906 ms (width 2),
 // 262k 0.3628 -> 0.3429 (width 4), 2^20 finish kernel 118.6 -> 91.4 us (width 8, tree, 2 waves per SIMD).
@@ -233,6 +235,9 @@ struct pbft_ctx {
   uint64_t* d_tally = nullptr;
   size_t tally_cap = 0;  // bytes
   uint64_t* t_signers = nullptr;
+  // pbft_verify_frames: the frames the host parser settled, as (index, record, head) patches (grow-only)
+  uint8_t* d_fpatch = nullptr;
+  size_t fpatch_cap = 0;  // bytes
 };
 
 #ifndef PBFT_ENV_SCHED
@@ -1010,6 +1015,7 @@ int pbft_verify_ctx_destroy(pbft_ctx* c) {
   c->adopt(nullptr);
   (void)hipFree(c->d_stage); (void)hipFree(c->d_bitmap); (void)hipFree(c->d_work); (void)hipFree(c->d_wk);
   (void)hipFree(c->d_tally);
+  (void)hipFree(c->d_fpatch);
   if (c->h_bitmap) (void)hipHostFree(c->h_bitmap);
   if (c->h_stage) (void)hipHostFree(c->h_stage);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -1989,6 +1995,156 @@ int pbft_verify_records(pbft_ctx* c, const uint8_t* rec, uint64_t N, uint64_t* o
   rc = pbft_verify_records_device(c, c->d_stage, N, c->d_bitmap, c->stream);
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(out, c->d_bitmap, words * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return PBFT_OK;
+}
+
+// ---- JSON frames decoded on the device (include/pbft_wire.h; kernels: wire_decode.hip) ----
+static_assert(sizeof(pbft_frame_head) == 24, "pbft_frame_head is 24 bytes");
+static int check_frames_args(const void* d_stream, const void* d_off, const void* d_len, const void* d_peer,
+                             uint32_t n_replicas, uint64_t N, const void* d_records, const void* d_heads) {
+  if (n_replicas == 0 || n_replicas > 65535) return set_err(PBFT_EINVAL, "n_replicas out of range");
+  if (N > ((uint64_t)1 << 32)) return set_err(PBFT_EINVAL, "more than 2^32 frames");
+  if (N && (!d_stream || !d_off || !d_len || !d_records || !d_heads))
+    return set_err(PBFT_EINVAL, "null frames argument");
+  if (((uintptr_t)d_stream & 15) || ((uintptr_t)d_off & 7) || ((uintptr_t)d_len & 3) || ((uintptr_t)d_peer & 1) ||
+      ((uintptr_t)d_records & 15) || ((uintptr_t)d_heads & 7))
+    return set_err(PBFT_EINVAL, "misaligned frames pointer");
+  return PBFT_OK;
+}
+
+int pbft_wire_decode_frames_device(pbft_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes, const uint64_t* d_off,
+                                   const uint32_t* d_len, const uint16_t* d_peer, uint32_t n_replicas, uint64_t N,
+                                   uint8_t* d_records, pbft_frame_head* d_heads, void* stream) {
+  if (!c) return set_err(PBFT_EINVAL, "null context");
+  int rc = check_frames_args(d_stream, d_off, d_len, d_peer, n_replicas, N, d_records, d_heads);
+  if (rc) return rc;
+  if (N == 0) return PBFT_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  HIP_TRY(launch_decode_frames(d_stream, stream_bytes, d_off, d_len, d_peer, n_replicas, N, d_records, d_heads, st));
+  return PBFT_OK;
+}
+
+int pbft_verify_frames_device(pbft_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes, const uint64_t* d_off,
+                              const uint32_t* d_len, const uint16_t* d_peer, uint32_t n_replicas, uint64_t N,
+                              uint8_t* d_records, pbft_frame_head* d_heads, uint64_t* dB, void* stream) {
+  if (!c) return set_err(PBFT_EINVAL, "null context");
+  int rc = check_frames_args(d_stream, d_off, d_len, d_peer, n_replicas, N, d_records, d_heads);
+  if (rc) return rc;
+  if (N && !dB) return set_err(PBFT_EINVAL, "null bitmap");
+  if ((uintptr_t)dB & 7) return set_err(PBFT_EINVAL, "misaligned frames pointer");
+  if (c->n_keys == 0) return set_err(PBFT_ENOKEYS, "pbft_verify_set_keys not called");
+  if (N == 0) return PBFT_OK;
+  rc = pbft_wire_decode_frames_device(c, d_stream, stream_bytes, d_off, d_len, d_peer, n_replicas, N, d_records,
+                                      d_heads, stream);
+  if (rc) return rc;
+  return pbft_verify_records_device(c, d_records, N, dB, stream);
+}
+
+// Device staging of the host form: records | heads | off | len | peer | (16-byte aligned) stream
+struct frames_layout {
+  size_t heads, off, len, peer, stream, total;
+  frames_layout(uint64_t N, uint64_t stream_bytes) {
+    heads = PBFT_RECORD_BYTES * (size_t)N;
+    off = heads + sizeof(pbft_frame_head) * (size_t)N;
+    len = off + 8 * (size_t)N;
+    peer = len + 4 * (size_t)N;
+    stream = (peer + 2 * (size_t)N + 15) & ~(size_t)15;
+    total = stream + (((size_t)stream_bytes + 15) & ~(size_t)15);
+  }
+};
+
+int pbft_verify_frames(pbft_ctx* c, const uint8_t* stream, uint64_t stream_bytes, const uint64_t* off,
+                       const uint32_t* flen, const uint16_t* peer, uint32_t n_replicas, uint64_t N, uint64_t* out,
+                       pbft_frame_head* heads_out, uint8_t* records_out) {
+  if (!c) return set_err(PBFT_EINVAL, "null context");
+  if (c->in_flight) return set_err(PBFT_EBUSY, "async batch in flight");
+  if (n_replicas == 0 || n_replicas > 65535) return set_err(PBFT_EINVAL, "n_replicas out of range");
+  if (N > ((uint64_t)1 << 32)) return set_err(PBFT_EINVAL, "more than 2^32 frames");
+  if (N && (!stream || !off || !flen || !out || !heads_out)) return set_err(PBFT_EINVAL, "null frames argument");
+  if (((uintptr_t)off & 7) || ((uintptr_t)flen & 3) || ((uintptr_t)peer & 1) || ((uintptr_t)out & 7) ||
+      ((uintptr_t)heads_out & 7))
+    return set_err(PBFT_EINVAL, "misaligned frames pointer");
+  for (uint64_t f = 0; f < N; ++f)
+    if (flen[f] > stream_bytes || off[f] > stream_bytes - flen[f])
+      return set_err(PBFT_EINVAL, "frame beyond the end of the stream");
+  if (c->n_keys == 0) return set_err(PBFT_ENOKEYS, "pbft_verify_set_keys not called");
+  if (N == 0) return PBFT_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  const uint64_t words = (N + 63) / 64;
+  const frames_layout lay(N, stream_bytes);
+  int rc = ensure_stage(c, lay.total + 256, words);
+  if (rc) return rc;
+  uint8_t* const d = c->d_stage;
+  pbft_frame_head* const d_heads = (pbft_frame_head*)(d + lay.heads);
+  HIP_TRY(hipMemcpyAsync(d + lay.stream, stream, stream_bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(d + lay.off, off, 8 * N, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(d + lay.len, flen, 4 * N, hipMemcpyHostToDevice, c->stream));
+  if (peer) HIP_TRY(hipMemcpyAsync(d + lay.peer, peer, 2 * N, hipMemcpyHostToDevice, c->stream));
+  rc = pbft_wire_decode_frames_device(c, d + lay.stream, stream_bytes, (const uint64_t*)(d + lay.off),
+                                      (const uint32_t*)(d + lay.len), peer ? (const uint16_t*)(d + lay.peer) : nullptr,
+                                      n_replicas, N, d, d_heads, c->stream);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(heads_out, d_heads, sizeof(pbft_frame_head) * N, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  // the frames the device deferred: the general parser, and the status rules of pbft_wire_decode_votes
+  std::vector<uint32_t> pidx;
+  std::vector<uint8_t> prec;
+  std::vector<pbft_frame_head> phead;
+  static thread_local char arena[1 << 16];  // (as pbft_wire_decode_votes: votes carry no operation)
+  for (uint64_t f = 0; f < N; ++f) {
+    pbft_frame_head& h = heads_out[f];
+    if (h.status != PBFT_WIRE_EDEFER) continue;
+    pbft_wire_msg m;
+    uint8_t st = PBFT_WIRE_OK;
+    if (pbft_wire_decode_json((const char*)stream + off[f], flen[f], &m, arena, sizeof arena) != 0)
+      st = PBFT_WIRE_EJSON;
+    else if (m.kind == PBFT_MSG_CLIENT_REQUEST) st = PBFT_WIRE_EKIND;
+    else if (!m.digest_ok) st = PBFT_WIRE_EDIGEST;
+    else if (!m.has_sig) st = PBFT_WIRE_EUNSIGNED;
+    else if (m.replica >= n_replicas) st = PBFT_WIRE_ESIGNER;
+    else if (peer && m.kind != PBFT_MSG_PREPREPARE && m.replica != peer[f]) st = PBFT_WIRE_ESIGNER;
+    h.status = st;
+    if (st != PBFT_WIRE_OK) continue;
+    h.view = m.view;
+    h.seq = m.seq;
+    h.key_idx = (uint16_t)m.replica;
+    h.kind = (uint8_t)m.kind;
+    uint8_t env[PBFT_ENVELOPE_BYTES];
+    pbft_envelope(env, (uint8_t)m.kind, m.view, m.seq, m.digest);
+    const uint16_t k = (uint16_t)m.replica;
+    prec.resize(prec.size() + PBFT_RECORD_BYTES);
+    uint8_t* const rec = prec.data() + prec.size() - PBFT_RECORD_BYTES;
+    pbft_records_pack(m.sig, m.sig + 32, &k, env, PBFT_ENVELOPE_BYTES, 1, rec);
+    pidx.push_back((uint32_t)f);
+    phead.push_back(h);
+  }
+  if (!pidx.empty()) {  // one H2D copy: indices | records | heads, then a scatter on the device
+    const size_t P = pidx.size();
+    const size_t o_rec = (4 * P + 15) & ~(size_t)15, o_head = o_rec + PBFT_RECORD_BYTES * P;
+    const size_t bytes = o_head + sizeof(pbft_frame_head) * P;
+    if (bytes > c->fpatch_cap) {
+      if (c->d_fpatch) HIP_TRY(hipFree(c->d_fpatch));
+      c->d_fpatch = nullptr;
+      c->fpatch_cap = 0;
+      const size_t cap = bytes + (bytes >> 2) + 4096;
+      if (hipMalloc(&c->d_fpatch, cap) != hipSuccess) return set_err(PBFT_ENOMEM, "frame patch alloc");
+      c->fpatch_cap = cap;
+    }
+    std::vector<uint8_t> buf(bytes, 0);
+    memcpy(buf.data(), pidx.data(), 4 * P);
+    memcpy(buf.data() + o_rec, prec.data(), PBFT_RECORD_BYTES * P);
+    memcpy(buf.data() + o_head, phead.data(), sizeof(pbft_frame_head) * P);
+    HIP_TRY(hipMemcpyAsync(c->d_fpatch, buf.data(), bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(launch_patch_frames((const uint32_t*)c->d_fpatch, c->d_fpatch + o_rec, c->d_fpatch + o_head, (uint32_t)P,
+                                N, d, d_heads, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // (buf is pageable and dies with this scope)
+  }
+  rc = pbft_verify_records_device(c, d, N, c->d_bitmap, c->stream);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(out, c->d_bitmap, words * 8, hipMemcpyDeviceToHost, c->stream));
+  if (records_out) HIP_TRY(hipMemcpyAsync(records_out, d, PBFT_RECORD_BYTES * N, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return PBFT_OK;
 }

@@ -345,6 +345,50 @@ class GpuBatchVerifier:
         check(self._lib.pbft_verify_records(self._ctx, _ptr(rec), n, _ptr(out)))
         return out
 
+    def verify_frames(self, stream, off, flen, peer=None, n_replicas: int | None = None):
+        """pbft_verify_frames: the JSON frames stream[off[f] : off[f] + flen[f]] (wire.frame_index) decoded on the GPU
+        -- what is not a canonical signed vote by the host's parser -- and verified.  peer: None or the authenticated
+        replica index of each frame's connection; n_replicas defaults to the installed key count.  Returns (bitmap
+        words, heads as a wire.FrameHead array, records (N, 160) uint8); heads["status"] is what
+        wire.decode_votes gives (plus the peer rule), bit f is set iff frame f is OK and its signature verifies."""
+        from .wire import FrameHead
+        buf = np.ascontiguousarray(np.frombuffer(stream, np.uint8) if isinstance(stream, (bytes, bytearray))
+                                   else stream, np.uint8).reshape(-1)
+        off = np.ascontiguousarray(off, np.uint64).reshape(-1)
+        flen = np.ascontiguousarray(flen, np.uint32).reshape(-1)
+        n = len(off)
+        if len(flen) != n:
+            raise ValueError("off and flen must have the same length")
+        if peer is not None:
+            peer = np.ascontiguousarray(peer, np.uint16).reshape(-1)
+            if len(peer) != n:
+                raise ValueError("peer must have one entry per frame")
+        out = np.zeros((n + 63) // 64, dtype=np.uint64)
+        heads = np.zeros(n, dtype=FrameHead)
+        records = np.zeros((n, 160), dtype=np.uint8)
+        check(self._lib.pbft_verify_frames(self._ctx, _ptr(buf), len(buf), _ptr(off), _ptr(flen),
+                                           _ptr(peer) if peer is not None else None,
+                                           self.n_keys if n_replicas is None else n_replicas, n, _ptr(out),
+                                           _ptr(heads), _ptr(records)))
+        return out, heads, records
+
+    def decode_frames_device(self, d_stream: int, stream_bytes: int, d_off: int, d_len: int, n_replicas: int, n: int,
+                             d_records: int, d_heads: int, d_peer: int = 0, stream: int = 0) -> None:
+        """pbft_wire_decode_frames_device: enqueue the decode of n frames (raw device pointers; d_stream 16-byte
+        aligned and readable up to stream_bytes rounded up to 16) into d_records (n x 160 B) and d_heads (n x 24 B).
+        Frames that are not canonical signed votes are marked wire.EDEFER."""
+        check(self._lib.pbft_wire_decode_frames_device(self._ctx, d_stream or None, stream_bytes, d_off or None,
+                                                       d_len or None, d_peer or None, n_replicas, n,
+                                                       d_records or None, d_heads or None, stream or None))
+
+    def verify_frames_device(self, d_stream: int, stream_bytes: int, d_off: int, d_len: int, n_replicas: int, n: int,
+                             d_records: int, d_heads: int, d_bitmap: int, d_peer: int = 0, stream: int = 0) -> None:
+        """pbft_verify_frames_device: decode_frames_device, then the verify of d_records on the same stream (reserve(n)
+        before capturing it into a graph)."""
+        check(self._lib.pbft_verify_frames_device(self._ctx, d_stream or None, stream_bytes, d_off or None,
+                                                  d_len or None, d_peer or None, n_replicas, n, d_records or None,
+                                                  d_heads or None, d_bitmap or None, stream or None))
+
     OPT_SPLIT_BELOW, OPT_FINISH_WIDTH, OPT_KEY_TABLE_BUDGET_MB, OPT_FINISH_TREE, OPT_LAT_SPLIT = 1, 2, 3, 4, 5
     OPT_KERNEL_TIMING = 7
     OPT_FINISH_WAVES = 8

@@ -17,7 +17,13 @@ from ._lib import PbftError, check, load
 PREPREPARE, PREPARE, COMMIT, CLIENT_REQUEST = 0, 1, 2, 3
 RECORD_BYTES = 160
 ENVELOPE = 85
-STATUS = {0: "ok", 1: "json", 2: "digest", 3: "unsigned", 4: "kind", 5: "signer"}
+STATUS = {0: "ok", 1: "json", 2: "digest", 3: "unsigned", 4: "kind", 5: "signer", 6: "defer"}
+EDEFER = 6  # PBFT_WIRE_EDEFER: not the canonical vote form (device decode only; verify_frames settles it)
+FRAME_MIN, FRAME_MAX = 336, 379  # byte lengths of a canonical signed vote
+# pbft_frame_head (include/pbft_wire.h): one per frame of decode_frames_device / verify_frames
+FrameHead = np.dtype([("view", "<u8"), ("seq", "<u8"), ("key_idx", "<u2"), ("kind", "u1"), ("status", "u1"),
+                      ("frame_len", "<u4")])
+assert FrameHead.itemsize == 24
 
 
 class _Msg(ctypes.Structure):
@@ -135,6 +141,20 @@ def decode_votes(stream: bytes, n_replicas: int, max_frames: int | None = None) 
                                      ctypes.byref(used)))
     f, r = nf.value, nr.value
     return Votes(st[:f], R[:r], S[:r], K[:r], M[:r], kd[:r], vw[:r], sq[:r], used.value)
+
+
+def frame_index(stream, max_frames: int | None = None):
+    """pbft_wire_frame_index: the varint scan of a stream of UviBytes frames; returns (off uint64[n], flen uint32[n],
+    consumed): frame f's body is stream[off[f] : off[f] + flen[f]], consumed the bytes of whole frames.  Raises on a
+    framing error."""
+    buf = np.ascontiguousarray(np.frombuffer(stream, np.uint8) if isinstance(stream, (bytes, bytearray))
+                               else stream, np.uint8).reshape(-1)
+    cap = len(buf) if max_frames is None else max_frames  # (a frame is at least its one varint byte)
+    off, flen = np.zeros(max(1, cap), np.uint64), np.zeros(max(1, cap), np.uint32)
+    nf, used = ctypes.c_uint64(), ctypes.c_uint64()
+    check(load().pbft_wire_frame_index(buf.ctypes.data if len(buf) else None, len(buf), cap, off.ctypes.data,
+                                       flen.ctypes.data, ctypes.byref(nf), ctypes.byref(used)))
+    return off[: nf.value].copy(), flen[: nf.value].copy(), used.value
 
 
 def records_pack(R, S, key_idx, msg, msg_stride: int = ENVELOPE) -> np.ndarray:
