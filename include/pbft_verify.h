@@ -320,6 +320,40 @@ int pbft_verify_votes_tally(pbft_ctx *ctx, const uint8_t *R, const uint8_t *S, c
                             const uint32_t *env_idx, const uint8_t *envelopes, uint32_t n_env, uint64_t N,
                             uint64_t *bitmap_out, uint64_t *signers_out, uint32_t *count_out);
 
+/* Envelope grouping: the step from rows that each carry their own 85-byte envelope (the frame decoder's 160-byte
+ * records, a batch's msg column) to the (env_idx, envelope table) pair the tally above and the votes forms take.
+ * Row i's envelope is the 85 bytes at d_msg + i * msg_stride.  Envelope e is the e-th distinct 85-byte string in row
+ * order, by first appearance -- what a Python dict filled row by row gives: d_env_idx[i] = e, d_envelopes[e] holds the
+ * bytes, d_n_env[0] is the number of distinct envelopes found.  All 85 bytes are the key: a Prepare and a Commit for
+ * one (view, seq, digest) are two envelopes.  The result is exact and does not depend on the hash seed, the launch
+ * geometry or the order in which atomics land.
+ * A row whose key index (the u16 at d_key_idx + i * key_stride bytes; d_key_idx NULL = none) is 0xFFFF is skipped: it
+ * takes part in nothing and gets env_idx 0xFFFFFFFF -- the frame decoder marks every frame that is not PBFT_WIRE_OK so.
+ * Overflow: d_n_env[0] may exceed env_cap; rows whose envelope's index is >= env_cap get 0xFFFFFFFF too, d_n_env[1]
+ * counts them, and the table's entries [min(n_env, env_cap), env_cap) are zero.  The votes forms read 0xFFFFFFFF as
+ * "bit 0" and the tally as "contributes nothing", so an undersized table loses votes, never miscounts them.
+ * msg_stride = 160 with d_msg = d_records + 64, d_key_idx = d_records + 150, key_stride = 160 reads wire records in
+ * place; msg_stride = 85 a plain column (any byte alignment).  Nothing is read beyond row N - 1's 85 bytes.
+ * d_envelopes is written for env_cap * 85 bytes (allocate 16 more, readable, if pbft_verify_votes_device is to read
+ * it); d_env_idx [N] and d_n_env [2] are 4-byte aligned, d_key_idx 2-byte.
+ * Enqueue only, on `stream` (NULL = the context's): five kernels -- fill the context's open-addressing table (u32
+ * slots, a power of two >= 2 N); one lane per row claims a slot or joins the one whose representative row has its
+ * bytes, after rows that agree have merged inside their wave; mark the representatives; prefix-sum the marks; write
+ * indices and table.  No copy or memset node and no host synchronisation, every loop bounded, no lane waits for
+ * another: capturable as a chain of kernel nodes.  The workspace (~12 bytes per row at a power of two, up to ~20
+ * above one) grows on first use of a larger N, which is then not capturable: call pbft_group_reserve(max_n) first.
+ * Calls of one context share the workspace and must be ordered, like its verify launches.
+ * PBFT_EINVAL: a null pointer that would be used (d_n_env always; d_msg, d_env_idx with N > 0; d_envelopes with
+ * env_cap > 0), a misaligned one, msg_stride < 85, key_stride < 2 or odd, env_cap = 0 with N > 0, N > 2^31.  N = 0
+ * writes d_n_env = {0, 0} and zeroes the table.  The hash of a row mixes all 85 bytes with a 64-bit seed the context
+ * draws on the host at first use (PBFT_OPT_GROUP_SEED fixes it), so a peer cannot aim at one probe chain. */
+int pbft_group_envelopes_device(pbft_ctx *ctx, const uint8_t *d_msg, uint32_t msg_stride,
+                                const uint16_t *d_key_idx, uint32_t key_stride,
+                                uint64_t N, uint32_t env_cap,
+                                uint32_t *d_env_idx /* [N] */, uint8_t *d_envelopes /* [env_cap][85] */,
+                                uint32_t *d_n_env /* [2] */, void *stream /* NULL = the context's */);
+int pbft_group_reserve(pbft_ctx *ctx, uint64_t max_n);
+
 /* Pre-size the verify workspace (~230 bytes of HBM per signature) for batches
  * of up to max_n signatures, so that later launches allocate nothing (required
  * before capturing pbft_verify_batch_device into a hipGraph). */
@@ -381,6 +415,12 @@ int pbft_sign_batch(pbft_ctx *ctx, const uint8_t *seeds, uint32_t n_seeds, const
  * SIMD trade priorities so that they progress together (instead of oldest-first); 0: 4-wave blocks; any other
  * value (default; env PBFT_COMB_PRIO) = by batch size: 8-wave blocks where they fit one per CU (the 131k shard). */
 #define PBFT_OPT_COMB_PRIO 13
+/* pbft_group_envelopes_device: the 64-bit seed of its row hash (default: drawn on the host at the context's first
+ * grouping call).  The output does not depend on it. */
+#define PBFT_OPT_GROUP_SEED 16
+/* Testing: keep only the low b bits of the row hash (0..64; default 64).  b = 0 sends every row down one probe
+ * chain; the output does not change, the time does. */
+#define PBFT_OPT_GROUP_HASH_BITS 17
 int pbft_verify_set_option(pbft_ctx *ctx, int option, uint64_t value);
 
 /* Diagnostics */

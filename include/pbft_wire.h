@@ -184,6 +184,36 @@ int pbft_verify_frames(pbft_ctx *ctx, const uint8_t *stream, uint64_t stream_byt
                        const uint32_t *flen, const uint16_t *peer, uint32_t n_replicas, uint64_t N,
                        uint64_t *bitmap_out, pbft_frame_head *heads_out, uint8_t *records_out);
 
+/* Frames in, quorums out.  Device, enqueue only, one stream: the decode; pbft_group_envelopes_device over d_records
+ * in place (envelope at +64, key index at +150, stride 160: a frame that is not PBFT_WIRE_OK has key index 0xFFFF and
+ * is skipped), which writes d_env_idx [N], d_envelopes [env_cap][85] and d_n_env [2]; pbft_verify_records_device, so
+ * d_bitmap is word for word what pbft_verify_frames_device writes for the same input; and pbft_tally_device with the
+ * records' key indices, the new d_env_idx, n_env = env_cap and n_signers = the installed key count, which writes
+ * d_signers [env_cap][ceil(n_keys / 64)] and d_count [env_cap] (table entries >= d_n_env[0] have empty sets and count
+ * 0).  No per-vote data has to leave the device between the socket's bytes and "these envelopes have 2f / 2f + 1
+ * distinct valid signers".  An env_cap below the number of distinct envelopes loses the later envelopes' votes (their
+ * rows get env_idx 0xFFFFFFFF, counted in d_n_env[1]), never miscounts.  Call pbft_verify_reserve(N) and
+ * pbft_group_reserve(N) before a capture.  PBFT_EINVAL as pbft_verify_frames_device and pbft_group_envelopes_device
+ * (env_cap = 0 with N > 0, N > 2^31), and for a null or misaligned output; a refused call has enqueued nothing.
+ * N = 0 writes d_n_env = {0, 0} and zeroes the table, the sets and the counts. */
+int pbft_verify_frames_tally_device(pbft_ctx *ctx, const uint8_t *d_stream, uint64_t stream_bytes,
+                                    const uint64_t *d_off, const uint32_t *d_len, const uint16_t *d_peer,
+                                    uint32_t n_replicas, uint64_t N, uint8_t *d_records, pbft_frame_head *d_heads,
+                                    uint64_t *d_bitmap, uint32_t env_cap, uint32_t *d_env_idx, uint8_t *d_envelopes,
+                                    uint32_t *d_n_env, uint64_t *d_signers, uint32_t *d_count, void *stream);
+
+/* Host, blocking: pbft_verify_frames' staging, its host settlement of the PBFT_WIRE_EDEFER frames and its patch, then
+ * group, verify and tally as above on the settled records.  Back per frame: heads_out, bitmap_out (both as
+ * pbft_verify_frames gives them) and, unless NULL, env_idx_out [N]; back per envelope: envelopes_out [env_cap][85],
+ * n_env_out [2], signers_out [env_cap][ceil(n_keys / 64)] and count_out [env_cap].  The 160-byte records stay on the
+ * device.  Argument checks and codes of pbft_verify_frames; PBFT_EINVAL also for env_cap = 0 with N > 0, N > 2^31 and
+ * a null output.  N = 0 zeroes the per-envelope outputs. */
+int pbft_verify_frames_tally(pbft_ctx *ctx, const uint8_t *stream, uint64_t stream_bytes, const uint64_t *off,
+                             const uint32_t *flen, const uint16_t *peer, uint32_t n_replicas, uint64_t N,
+                             uint32_t env_cap, uint64_t *bitmap_out, pbft_frame_head *heads_out,
+                             uint32_t *env_idx_out, uint8_t *envelopes_out, uint32_t *n_env_out,
+                             uint64_t *signers_out, uint32_t *count_out);
+
 #ifdef __cplusplus
 }
 #endif

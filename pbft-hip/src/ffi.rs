@@ -254,6 +254,10 @@ extern "C" {
     pub fn pbft_verify_votes_tally(ctx: *mut pbft_ctx, r: *const u8, s: *const u8, key_idx: *const u16,
                                    env_idx: *const u32, envelopes: *const u8, n_env: u32, n: u64,
                                    bitmap_out: *mut u64, signers_out: *mut u64, count_out: *mut u32) -> c_int;
+    pub fn pbft_group_envelopes_device(ctx: *mut pbft_ctx, d_msg: *const u8, msg_stride: u32, d_key_idx: *const u16,
+                                       key_stride: u32, n: u64, env_cap: u32, d_env_idx: *mut u32,
+                                       d_envelopes: *mut u8, d_n_env: *mut u32, stream: *mut c_void) -> c_int;
+    pub fn pbft_group_reserve(ctx: *mut pbft_ctx, max_n: u64) -> c_int;
     pub fn pbft_verify_reserve(ctx: *mut pbft_ctx, max_n: u64) -> c_int;
     pub fn pbft_digest_blake2b512(ctx: *mut pbft_ctx, data: *const u8, offsets: *const u64, lens: *const u32,
                                   n: u64, out: *mut u8) -> c_int;
@@ -342,4 +346,15 @@ extern "C" {
     pub fn pbft_verify_frames(ctx: *mut pbft_ctx, stream: *const u8, stream_bytes: u64, off: *const u64,
                               flen: *const u32, peer: *const u16, n_replicas: u32, n: u64, bitmap_out: *mut u64,
                               heads_out: *mut pbft_frame_head, records_out: *mut u8) -> c_int;
+    pub fn pbft_verify_frames_tally_device(ctx: *mut pbft_ctx, d_stream: *const u8, stream_bytes: u64,
+                                           d_off: *const u64, d_len: *const u32, d_peer: *const u16,
+                                           n_replicas: u32, n: u64, d_records: *mut u8,
+                                           d_heads: *mut pbft_frame_head, d_bitmap: *mut u64, env_cap: u32,
+                                           d_env_idx: *mut u32, d_envelopes: *mut u8, d_n_env: *mut u32,
+                                           d_signers: *mut u64, d_count: *mut u32, stream: *mut c_void) -> c_int;
+    pub fn pbft_verify_frames_tally(ctx: *mut pbft_ctx, stream: *const u8, stream_bytes: u64, off: *const u64,
+                                    flen: *const u32, peer: *const u16, n_replicas: u32, n: u64, env_cap: u32,
+                                    bitmap_out: *mut u64, heads_out: *mut pbft_frame_head, env_idx_out: *mut u32,
+                                    envelopes_out: *mut u8, n_env_out: *mut u32, signers_out: *mut u64,
+                                    count_out: *mut u32) -> c_int;
 }

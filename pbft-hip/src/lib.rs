@@ -185,6 +185,23 @@ impl Tally {
 /// Head of one decoded frame (ffi::pbft_frame_head): status, and view / seq / kind / signer of an OK frame.
 pub type FrameHead = ffi::pbft_frame_head;
 
+/// Result of `GpuVerifier::verify_frames_tally`: per frame the bitmap and the heads, per envelope -- in order of
+/// first appearance in the stream -- its 85 bytes with its signer set and count (`tally`, indexed like `envelopes`).
+#[derive(Clone, Debug)]
+pub struct FramesTally {
+    pub bitmap: Bitmap,
+    pub heads: Vec<FrameHead>,
+    /// The distinct envelopes kept: min(envelopes_found, env_cap) of them.
+    pub envelopes: Vec<[u8; 85]>,
+    pub tally: Tally,
+    /// Distinct envelopes in the stream (may exceed env_cap).
+    pub envelopes_found: u32,
+    /// OK frames whose envelope did not fit env_cap: their votes are in no set.
+    pub rows_lost: u32,
+    /// Bytes of whole frames (an incomplete last frame stays with the caller).
+    pub consumed: usize,
+}
+
 /// Handle of one submitted batch.
 #[derive(Debug, PartialEq, Eq)]
 pub struct Ticket(pub u64);
@@ -294,6 +311,48 @@ impl GpuVerifier {
                                     out.0.as_mut_ptr(), heads.as_mut_ptr(), ptr::null_mut())
         })?;
         Ok((out, heads, used as usize))
+    }
+    /// `verify_frames` with the frames grouped by envelope and tallied on the GPU (pbft_verify_frames_tally): from
+    /// the bytes a socket delivered to "these envelopes have 2f / 2f + 1 distinct valid signers" in one call.  Nothing
+    /// per vote comes back but the heads and the bitmap; per envelope come its 85 bytes, its signer set and its count.
+    /// `env_cap`: room for that many distinct envelopes -- later ones lose their votes (`rows_lost`), none is miscounted.
+    pub fn verify_frames_tally(&mut self, stream: &[u8], peer: Option<u16>, n_replicas: u32,
+                               env_cap: u32) -> Result<FramesTally> {
+        if self.inflight.is_some() {
+            return Err(Error { code: ffi::PBFT_EBUSY, message: "one batch in flight per context".into() });
+        }
+        let (mut wb, mut wa, mut n_keys) = (0u32, 0u32, 0u32);
+        check(unsafe { ffi::pbft_verify_ctx_info(self.ctx, &mut wb, &mut wa, &mut n_keys) })?;
+        let cap = stream.len(); // a frame is at least its one varint byte
+        let (mut off, mut flen) = (vec![0u64; cap], vec![0u32; cap]);
+        let (mut n, mut used) = (0u64, 0u64);
+        check(unsafe {
+            ffi::pbft_wire_frame_index(stream.as_ptr(), stream.len(), cap as u64, off.as_mut_ptr(), flen.as_mut_ptr(),
+                                       &mut n, &mut used)
+        })?;
+        let n = n as usize;
+        let peers = peer.map(|p| vec![p; n]);
+        let words_per_env = (n_keys as usize + 63) / 64;
+        let cap_env = env_cap as usize;
+        let mut bitmap = Bitmap::zeros(n);
+        let mut heads = vec![FrameHead::default(); n];
+        let mut envelopes = vec![[0u8; 85]; cap_env];
+        let mut n_env = [0u32; 2];
+        let mut tally = Tally { signers: vec![0u64; cap_env * words_per_env], counts: vec![0u32; cap_env],
+                                words_per_env };
+        check(unsafe {
+            ffi::pbft_verify_frames_tally(self.ctx, stream.as_ptr(), stream.len() as u64, off.as_ptr(), flen.as_ptr(),
+                                          peers.as_ref().map_or(ptr::null(), |p| p.as_ptr()), n_replicas, n as u64,
+                                          env_cap, bitmap.0.as_mut_ptr(), heads.as_mut_ptr(), ptr::null_mut(),
+                                          envelopes.as_mut_ptr() as *mut u8, n_env.as_mut_ptr(),
+                                          tally.signers.as_mut_ptr(), tally.counts.as_mut_ptr())
+        })?;
+        let kept = (n_env[0] as usize).min(cap_env);
+        envelopes.truncate(kept);
+        tally.signers.truncate(kept * words_per_env);
+        tally.counts.truncate(kept);
+        Ok(FramesTally { bitmap, heads, envelopes, tally, envelopes_found: n_env[0], rows_lost: n_env[1],
+                         consumed: used as usize })
     }
     /// Another context on the same GPU sharing this one's tables (own HIP stream).
     pub fn try_clone(&self) -> Result<Self> {

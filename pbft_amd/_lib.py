@@ -22,12 +22,12 @@ EXPORTS = (
     "pbft_verify_set_option", "pbft_verify_batch_device_pipelined", "pbft_verify_votes", "pbft_verify_votes_device",
     "pbft_verify_votes_async", "pbft_verify_votes_stage", "pbft_verify_votes_submit",
     "pbft_multi_create", "pbft_multi_destroy", "pbft_verify_batch_device_multi", "pbft_multi_sync",
-    "pbft_tally_device", "pbft_verify_votes_tally",
+    "pbft_tally_device", "pbft_verify_votes_tally", "pbft_group_envelopes_device", "pbft_group_reserve",
     # include/pbft_wire.h
     "pbft_uvi_encode", "pbft_uvi_decode", "pbft_wire_encode_json", "pbft_wire_encode_frame",
     "pbft_wire_decode_json", "pbft_wire_decode_votes", "pbft_records_pack", "pbft_verify_records_device",
     "pbft_verify_records", "pbft_wire_encode_votes", "pbft_wire_frame_index", "pbft_wire_decode_frames_device",
-    "pbft_verify_frames_device", "pbft_verify_frames",
+    "pbft_verify_frames_device", "pbft_verify_frames", "pbft_verify_frames_tally_device", "pbft_verify_frames_tally",
 )
 
 ERRORS = {0: "PBFT_OK", -1: "PBFT_EINVAL", -2: "PBFT_EHIP", -3: "PBFT_ENOKEYS",
@@ -122,6 +122,11 @@ def load() -> ctypes.CDLL:
         "pbft_wire_decode_frames_device": (i32, [vp, vp, u64, vp, vp, vp, u32, u64, vp, vp, vp]),
         "pbft_verify_frames_device": (i32, [vp, vp, u64, vp, vp, vp, u32, u64, vp, vp, vp, vp]),
         "pbft_verify_frames": (i32, [vp, vp, u64, vp, vp, vp, u32, u64, vp, vp, vp]),
+        "pbft_group_envelopes_device": (i32, [vp, vp, u32, vp, u32, u64, u32, vp, vp, vp, vp]),
+        "pbft_group_reserve": (i32, [vp, u64]),
+        "pbft_verify_frames_tally_device": (i32, [vp, vp, u64, vp, vp, vp, u32, u64, vp, vp, vp, u32, vp, vp, vp, vp,
+                                                  vp, vp]),
+        "pbft_verify_frames_tally": (i32, [vp, vp, u64, vp, vp, vp, u32, u64, u32, vp, vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

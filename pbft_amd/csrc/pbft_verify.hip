@@ -21,6 +21,7 @@
 #include <atomic>
 #include <chrono>
 #include <mutex>
+#include <random>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -34,6 +35,7 @@
 using namespace pbft;
 #include "verify_kernels.h"
 #include "tally_kernels.h"
+#include "group_kernels.h"
 #include "wire_decode_kernels.h"
 // Finish configuration by batch size (signatures per lane, product tree, waves per SIMD), measured on MI355X
 // with the lane-parallel wave inversion (profiles/r03/ab_finish.txt): 131k 0.2115 -> 0.1906 ms (width 2),
@@ -238,6 +240,13 @@ struct pbft_ctx {
   // pbft_verify_frames: the frames the host parser settled, as (index, record, head) patches (grow-only)
   uint8_t* d_fpatch = nullptr;
   size_t fpatch_cap = 0;  // bytes
+  // pbft_group_envelopes_device: table, slots, marks and their prefix (grow-only; pbft_group_reserve), the hash
+  // seed (drawn at first use unless PBFT_OPT_GROUP_SEED set it) and the hash bits kept (PBFT_OPT_GROUP_HASH_BITS)
+  uint8_t* d_group = nullptr;
+  size_t group_cap = 0;  // bytes
+  uint64_t group_seed = 0;
+  bool group_seeded = false;
+  uint32_t group_hash_bits = 64;
 };
 
 #ifndef PBFT_ENV_SCHED
@@ -1016,6 +1025,7 @@ int pbft_verify_ctx_destroy(pbft_ctx* c) {
   (void)hipFree(c->d_stage); (void)hipFree(c->d_bitmap); (void)hipFree(c->d_work); (void)hipFree(c->d_wk);
   (void)hipFree(c->d_tally);
   (void)hipFree(c->d_fpatch);
+  (void)hipFree(c->d_group);
   if (c->h_bitmap) (void)hipHostFree(c->h_bitmap);
   if (c->h_stage) (void)hipHostFree(c->h_stage);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -1923,6 +1933,60 @@ int pbft_tally_device(pbft_ctx* c, const uint64_t* dB, const uint16_t* dK, uint3
   return PBFT_OK;
 }
 
+// ---- envelope grouping (include/pbft_verify.h; kernels: group.hip) ----
+static int ensure_group(pbft_ctx* c, uint64_t N) {
+  const size_t bytes = group_ws_bytes(N);
+  if (bytes <= c->group_cap) return PBFT_OK;
+  if (c->d_group) HIP_TRY(hipFree(c->d_group));  // (waits for the device: an earlier call may still use it)
+  c->d_group = nullptr;
+  c->group_cap = 0;
+  if (hipMalloc(&c->d_group, bytes) != hipSuccess) return set_err(PBFT_ENOMEM, "group workspace alloc");
+  c->group_cap = bytes;
+  return PBFT_OK;
+}
+
+static int check_group_args(const void* d_msg, uint32_t msg_stride, const void* dK, uint32_t key_stride, uint64_t N,
+                            uint32_t env_cap, const void* d_env_idx, const void* d_envelopes, const void* d_n_env) {
+  if (N > GROUP_MAX_ROWS) return set_err(PBFT_EINVAL, "more than 2^31 rows to group");
+  if (msg_stride < PBFT_ENVELOPE_LEN || key_stride < 2 || (key_stride & 1))
+    return set_err(PBFT_EINVAL, "bad group strides");
+  if (N && env_cap == 0) return set_err(PBFT_EINVAL, "env_cap is 0");
+  if (!d_n_env || (N && (!d_msg || !d_env_idx)) || (env_cap && !d_envelopes))
+    return set_err(PBFT_EINVAL, "null group argument");
+  if (((uintptr_t)d_env_idx & 3) || ((uintptr_t)d_n_env & 3) || ((uintptr_t)dK & 1))
+    return set_err(PBFT_EINVAL, "misaligned group pointer");
+  return PBFT_OK;
+}
+
+// Five launches on the caller's stream.  The workspace grows here only when the call is larger than every one before
+// it and than pbft_group_reserve.
+int pbft_group_envelopes_device(pbft_ctx* c, const uint8_t* d_msg, uint32_t msg_stride, const uint16_t* dK,
+                                uint32_t key_stride, uint64_t N, uint32_t env_cap, uint32_t* d_env_idx,
+                                uint8_t* d_envelopes, uint32_t* d_n_env, void* stream) {
+  if (!c) return set_err(PBFT_EINVAL, "null context");
+  int rc = check_group_args(d_msg, msg_stride, dK, key_stride, N, env_cap, d_env_idx, d_envelopes, d_n_env);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  rc = ensure_group(c, N);
+  if (rc) return rc;
+  if (!c->group_seeded) {  // drawn on the host, once: a peer cannot aim its envelopes at one probe chain
+    std::random_device rd;
+    c->group_seed = ((uint64_t)rd() << 32) ^ rd() ^ (uint64_t)std::chrono::steady_clock::now().time_since_epoch().count();
+    c->group_seeded = true;
+  }
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  HIP_TRY(launch_group(d_msg, msg_stride, (const uint8_t*)dK, key_stride, N, env_cap, c->group_seed,
+                       c->group_hash_bits, c->d_group, d_env_idx, d_envelopes, d_n_env, st));
+  return PBFT_OK;
+}
+
+int pbft_group_reserve(pbft_ctx* c, uint64_t max_n) {
+  if (!c) return set_err(PBFT_EINVAL, "null context");
+  if (max_n > GROUP_MAX_ROWS) return set_err(PBFT_EINVAL, "more than 2^31 rows to group");
+  HIP_TRY(hipSetDevice(c->device));
+  return ensure_group(c, max_n);
+}
+
 // pbft_verify_votes with every chunk tallied on its own stream while its columns are resident (the staging keeps
 // VOTES_BUFS chunks, a batch may have more), all into one zeroed set -- OR is idempotent, so the chunks fold like
 // PBFT_TALLY_ACCUMULATE pieces; then the counts and the copies back on the context stream, which follows both.
@@ -2055,9 +2119,10 @@ struct frames_layout {
   }
 };
 
-int pbft_verify_frames(pbft_ctx* c, const uint8_t* stream, uint64_t stream_bytes, const uint64_t* off,
-                       const uint32_t* flen, const uint16_t* peer, uint32_t n_replicas, uint64_t N, uint64_t* out,
-                       pbft_frame_head* heads_out, uint8_t* records_out) {
+// The argument checks of the host forms (pbft_verify_frames, pbft_verify_frames_tally)
+static int check_host_frames_args(pbft_ctx* c, const uint8_t* stream, uint64_t stream_bytes, const uint64_t* off,
+                                  const uint32_t* flen, const uint16_t* peer, uint32_t n_replicas, uint64_t N,
+                                  const uint64_t* out, const pbft_frame_head* heads_out) {
   if (!c) return set_err(PBFT_EINVAL, "null context");
   if (c->in_flight) return set_err(PBFT_EBUSY, "async batch in flight");
   if (n_replicas == 0 || n_replicas > 65535) return set_err(PBFT_EINVAL, "n_replicas out of range");
@@ -2070,11 +2135,17 @@ int pbft_verify_frames(pbft_ctx* c, const uint8_t* stream, uint64_t stream_bytes
     if (flen[f] > stream_bytes || off[f] > stream_bytes - flen[f])
       return set_err(PBFT_EINVAL, "frame beyond the end of the stream");
   if (c->n_keys == 0) return set_err(PBFT_ENOKEYS, "pbft_verify_set_keys not called");
-  if (N == 0) return PBFT_OK;
-  HIP_TRY(hipSetDevice(c->device));
+  return PBFT_OK;
+}
+
+// The front half of the host forms, N > 0: stream and index into the device staging (laid out by `lay`, with `extra`
+// bytes behind it for the caller), the decode, the heads back, the host's word on every deferred frame, and the
+// patch of those that became OK.  Returns with all N records and heads settled on the device and the stream idle.
+static int frames_stage_decode(pbft_ctx* c, const uint8_t* stream, uint64_t stream_bytes, const uint64_t* off,
+                               const uint32_t* flen, const uint16_t* peer, uint32_t n_replicas, uint64_t N,
+                               pbft_frame_head* heads_out, const frames_layout& lay, size_t extra) {
   const uint64_t words = (N + 63) / 64;
-  const frames_layout lay(N, stream_bytes);
-  int rc = ensure_stage(c, lay.total + 256, words);
+  int rc = ensure_stage(c, lay.total + extra + 256, words);
   if (rc) return rc;
   uint8_t* const d = c->d_stage;
   pbft_frame_head* const d_heads = (pbft_frame_head*)(d + lay.heads);
@@ -2141,10 +2212,113 @@ int pbft_verify_frames(pbft_ctx* c, const uint8_t* stream, uint64_t stream_bytes
                                 N, d, d_heads, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));  // (buf is pageable and dies with this scope)
   }
+  return PBFT_OK;
+}
+
+int pbft_verify_frames(pbft_ctx* c, const uint8_t* stream, uint64_t stream_bytes, const uint64_t* off,
+                       const uint32_t* flen, const uint16_t* peer, uint32_t n_replicas, uint64_t N, uint64_t* out,
+                       pbft_frame_head* heads_out, uint8_t* records_out) {
+  int rc = check_host_frames_args(c, stream, stream_bytes, off, flen, peer, n_replicas, N, out, heads_out);
+  if (rc) return rc;
+  if (N == 0) return PBFT_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  const uint64_t words = (N + 63) / 64;
+  const frames_layout lay(N, stream_bytes);
+  rc = frames_stage_decode(c, stream, stream_bytes, off, flen, peer, n_replicas, N, heads_out, lay, 0);
+  if (rc) return rc;
+  uint8_t* const d = c->d_stage;
   rc = pbft_verify_records_device(c, d, N, c->d_bitmap, c->stream);
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(out, c->d_bitmap, words * 8, hipMemcpyDeviceToHost, c->stream));
   if (records_out) HIP_TRY(hipMemcpyAsync(records_out, d, PBFT_RECORD_BYTES * N, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return PBFT_OK;
+}
+
+// ---- frames in, quorums out: decode, group, verify, tally on one stream ----
+int pbft_verify_frames_tally_device(pbft_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes, const uint64_t* d_off,
+                                    const uint32_t* d_len, const uint16_t* d_peer, uint32_t n_replicas, uint64_t N,
+                                    uint8_t* d_records, pbft_frame_head* d_heads, uint64_t* dB, uint32_t env_cap,
+                                    uint32_t* d_env_idx, uint8_t* d_envelopes, uint32_t* d_n_env, uint64_t* d_signers,
+                                    uint32_t* d_count, void* stream) {
+  if (!c) return set_err(PBFT_EINVAL, "null context");
+  // every check of every step first: a refused call has written nothing
+  int rc = check_frames_args(d_stream, d_off, d_len, d_peer, n_replicas, N, d_records, d_heads);
+  if (rc) return rc;
+  if (N && !dB) return set_err(PBFT_EINVAL, "null bitmap");
+  if ((uintptr_t)dB & 7) return set_err(PBFT_EINVAL, "misaligned frames pointer");
+  rc = check_group_args(d_records, PBFT_RECORD_BYTES, d_records, PBFT_RECORD_BYTES, N, env_cap, d_env_idx,
+                        d_envelopes, d_n_env);
+  if (rc) return rc;
+  if (env_cap && (!d_signers || !d_count)) return set_err(PBFT_EINVAL, "null tally output");
+  if (((uintptr_t)d_signers & 7) || ((uintptr_t)d_count & 3)) return set_err(PBFT_EINVAL, "misaligned tally pointer");
+  if (c->n_keys == 0) return set_err(PBFT_ENOKEYS, "pbft_verify_set_keys not called");
+  const uint16_t* const d_key = (const uint16_t*)(d_records + 150);
+  if (N) {
+    rc = pbft_wire_decode_frames_device(c, d_stream, stream_bytes, d_off, d_len, d_peer, n_replicas, N, d_records,
+                                        d_heads, stream);
+    if (rc) return rc;
+  }
+  rc = pbft_group_envelopes_device(c, d_records + 64, PBFT_RECORD_BYTES, d_key, PBFT_RECORD_BYTES, N, env_cap,
+                                   d_env_idx, d_envelopes, d_n_env, stream);
+  if (rc) return rc;
+  if (N) {
+    rc = pbft_verify_records_device(c, d_records, N, dB, stream);
+    if (rc) return rc;
+  }
+  return pbft_tally_device(c, dB, d_key, PBFT_RECORD_BYTES, d_env_idx, 4, N, env_cap, c->n_keys, 0, d_signers,
+                           d_count, stream);
+}
+
+int pbft_verify_frames_tally(pbft_ctx* c, const uint8_t* stream, uint64_t stream_bytes, const uint64_t* off,
+                             const uint32_t* flen, const uint16_t* peer, uint32_t n_replicas, uint64_t N,
+                             uint32_t env_cap, uint64_t* out, pbft_frame_head* heads_out, uint32_t* env_idx_out,
+                             uint8_t* envelopes_out, uint32_t* n_env_out, uint64_t* signers_out,
+                             uint32_t* count_out) {
+  int rc = check_host_frames_args(c, stream, stream_bytes, off, flen, peer, n_replicas, N, out, heads_out);
+  if (rc) return rc;
+  if (N && env_cap == 0) return set_err(PBFT_EINVAL, "env_cap is 0");
+  if (!n_env_out || (env_cap && (!envelopes_out || !signers_out || !count_out)))
+    return set_err(PBFT_EINVAL, "null tally output");
+  if (N > GROUP_MAX_ROWS) return set_err(PBFT_EINVAL, "more than 2^31 rows to group");
+  const uint32_t W = tally_words(c->n_keys);
+  const size_t env_bytes = (size_t)env_cap * PBFT_ENVELOPE_LEN, set_bytes = (size_t)env_cap * W * 8,
+               cnt_bytes = (size_t)env_cap * 4;
+  if (N == 0) {  // no frame: no envelope, empty sets
+    n_env_out[0] = n_env_out[1] = 0;
+    if (env_cap) {
+      memset(envelopes_out, 0, env_bytes);
+      memset(signers_out, 0, set_bytes);
+      memset(count_out, 0, cnt_bytes);
+    }
+    return PBFT_OK;
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  const uint64_t words = (N + 63) / 64;
+  const frames_layout lay(N, stream_bytes);
+  // behind the frames staging: env_idx | envelopes (+16) | n_env | signer sets | counts
+  const size_t o_idx = lay.total, o_env = o_idx + ((4 * (size_t)N + 15) & ~(size_t)15),
+               o_n = o_env + ((env_bytes + 16 + 15) & ~(size_t)15), o_set = o_n + 16, o_cnt = o_set + set_bytes,
+               extra = o_cnt + cnt_bytes - lay.total;
+  rc = frames_stage_decode(c, stream, stream_bytes, off, flen, peer, n_replicas, N, heads_out, lay, extra);
+  if (rc) return rc;
+  uint8_t* const d = c->d_stage;
+  uint32_t* const d_idx = (uint32_t*)(d + o_idx);
+  const uint16_t* const d_key = (const uint16_t*)(d + 150);
+  rc = pbft_group_envelopes_device(c, d + 64, PBFT_RECORD_BYTES, d_key, PBFT_RECORD_BYTES, N, env_cap, d_idx,
+                                   d + o_env, (uint32_t*)(d + o_n), c->stream);
+  if (rc) return rc;
+  rc = pbft_verify_records_device(c, d, N, c->d_bitmap, c->stream);
+  if (rc) return rc;
+  rc = pbft_tally_device(c, c->d_bitmap, d_key, PBFT_RECORD_BYTES, d_idx, 4, N, env_cap, c->n_keys, 0,
+                         (uint64_t*)(d + o_set), (uint32_t*)(d + o_cnt), c->stream);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(out, c->d_bitmap, words * 8, hipMemcpyDeviceToHost, c->stream));
+  if (env_idx_out) HIP_TRY(hipMemcpyAsync(env_idx_out, d_idx, 4 * N, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(envelopes_out, d + o_env, env_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(n_env_out, d + o_n, 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(signers_out, d + o_set, set_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(count_out, d + o_cnt, cnt_bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return PBFT_OK;
 }
@@ -2286,6 +2460,14 @@ int pbft_verify_set_option(pbft_ctx* c, int option, uint64_t value) {
     case PBFT_OPT_FAULT_INJECT:
       if (value > 2) return set_err(PBFT_EINVAL, "fault injection point");
       c->fault_inject = (int)value;
+      return PBFT_OK;
+    case PBFT_OPT_GROUP_SEED:
+      c->group_seed = value;
+      c->group_seeded = true;
+      return PBFT_OK;
+    case PBFT_OPT_GROUP_HASH_BITS:
+      if (value > 64) return set_err(PBFT_EINVAL, "group hash bits");
+      c->group_hash_bits = (uint32_t)value;
       return PBFT_OK;
   }
   return set_err(PBFT_EINVAL, "unknown option");

@@ -97,6 +97,40 @@ def tally_reference(bits, key_idx, env_idx, n_env: int, n_signers: int):
     return signers, member.sum(axis=1).astype(np.uint32)
 
 
+ENV_NONE = 0xFFFFFFFF  # env_idx of a row that pbft_group_envelopes_device skipped or that env_cap left out
+
+
+def group_reference(msg_rows, skip_mask, env_cap: int):
+    """The semantics of pbft_group_envelopes_device in numpy: (env_idx, envelopes, n_env).  msg_rows is (N, >= 85)
+    uint8, of which the first 85 bytes of a row are its envelope; skip_mask: None or bool per row (the rows whose key
+    index is 0xFFFF).  Envelope e is the e-th distinct 85-byte string in row order, by first appearance -- a dict
+    filled row by row: env_idx[i] = e (uint32), envelopes (env_cap, 85) uint8 holds the first env_cap of them and
+    zeros behind, n_env = [distinct envelopes found (may exceed env_cap), rows that env_cap left without an index]
+    (uint32).  Skipped rows, and rows whose envelope's index is >= env_cap, get ENV_NONE."""
+    rows = np.ascontiguousarray(np.asarray(msg_rows, dtype=np.uint8))
+    rows = rows.reshape(len(rows), -1)[:, :85] if len(rows) else rows.reshape(0, 85)
+    n = len(rows)
+    skip = np.zeros(n, bool) if skip_mask is None else np.asarray(skip_mask).astype(bool).reshape(-1)
+    if len(skip) != n:
+        raise ValueError("skip_mask must have one entry per row")
+    if n and env_cap <= 0:
+        raise ValueError("env_cap must be positive")
+    seen: dict = {}
+    env_idx = np.full(n, ENV_NONE, dtype=np.uint32)
+    envelopes = np.zeros((env_cap, 85), dtype=np.uint8)
+    lost = 0
+    for i in range(n):
+        if skip[i]:
+            continue
+        e = seen.setdefault(rows[i].tobytes(), len(seen))
+        if e < env_cap:
+            env_idx[i] = e
+            envelopes[e] = rows[i]
+        else:
+            lost += 1
+    return env_idx, envelopes, np.array([len(seen), lost], dtype=np.uint32)
+
+
 def quorum(counts, need: int) -> np.ndarray:
     """Envelopes with at least `need` distinct valid signers (2f for prepared, 2f + 1 for committed-local:
     src/behavior.rs:177-182, :214-223); bool per envelope."""
@@ -389,6 +423,65 @@ class GpuBatchVerifier:
                                                   d_len or None, d_peer or None, n_replicas, n, d_records or None,
                                                   d_heads or None, d_bitmap or None, stream or None))
 
+    def group_reserve(self, max_n: int) -> None:
+        """pbft_group_reserve: pre-size the grouping workspace (required before capturing group_envelopes_device or
+        verify_frames_tally_device into a graph)."""
+        check(self._lib.pbft_group_reserve(self._ctx, max_n))
+
+    def group_envelopes_device(self, d_msg: int, n: int, env_cap: int, d_env_idx: int, d_envelopes: int,
+                               d_n_env: int, msg_stride: int = 85, d_key_idx: int = 0, key_stride: int = 2,
+                               stream: int = 0) -> None:
+        """pbft_group_envelopes_device: enqueue the grouping of n rows (raw device pointers; row i's envelope at
+        d_msg + i * msg_stride; d_key_idx 0 or a u16 per row with stride key_stride, 0xFFFF = skip the row) into
+        d_env_idx [n] u32, d_envelopes [env_cap][85] and d_n_env [2] u32 -- see group_reference."""
+        check(self._lib.pbft_group_envelopes_device(self._ctx, d_msg or None, msg_stride, d_key_idx or None,
+                                                    key_stride, n, env_cap, d_env_idx or None, d_envelopes or None,
+                                                    d_n_env or None, stream or None))
+
+    def verify_frames_tally_device(self, d_stream: int, stream_bytes: int, d_off: int, d_len: int, n_replicas: int,
+                                   n: int, d_records: int, d_heads: int, d_bitmap: int, env_cap: int, d_env_idx: int,
+                                   d_envelopes: int, d_n_env: int, d_signers: int, d_count: int, d_peer: int = 0,
+                                   stream: int = 0) -> None:
+        """pbft_verify_frames_tally_device: decode, group, verify and tally of n frames on one stream (reserve(n) and
+        group_reserve(n) before capturing it into a graph)."""
+        check(self._lib.pbft_verify_frames_tally_device(
+            self._ctx, d_stream or None, stream_bytes, d_off or None, d_len or None, d_peer or None, n_replicas, n,
+            d_records or None, d_heads or None, d_bitmap or None, env_cap, d_env_idx or None, d_envelopes or None,
+            d_n_env or None, d_signers or None, d_count or None, stream or None))
+
+    def verify_frames_tally(self, stream, off, flen, env_cap: int, peer=None, n_replicas: int | None = None,
+                            want_env_idx: bool = True):
+        """pbft_verify_frames_tally: verify_frames, with the frames grouped by envelope and tallied on the GPU.
+        Returns (bitmap words, heads, env_idx (N,) uint32 or None, envelopes (env_cap, 85) uint8, n_env (2,) uint32,
+        signers (env_cap, W) uint64, counts (env_cap,) uint32): quorum(counts, 2 * f) answers Pbft::prepared for
+        every envelope at once."""
+        from .wire import FrameHead
+        buf = np.ascontiguousarray(np.frombuffer(stream, np.uint8) if isinstance(stream, (bytes, bytearray))
+                                   else stream, np.uint8).reshape(-1)
+        off = np.ascontiguousarray(off, np.uint64).reshape(-1)
+        flen = np.ascontiguousarray(flen, np.uint32).reshape(-1)
+        n = len(off)
+        if len(flen) != n:
+            raise ValueError("off and flen must have the same length")
+        if peer is not None:
+            peer = np.ascontiguousarray(peer, np.uint16).reshape(-1)
+            if len(peer) != n:
+                raise ValueError("peer must have one entry per frame")
+        out = np.zeros((n + 63) // 64, dtype=np.uint64)
+        heads = np.zeros(n, dtype=FrameHead)
+        env_idx = np.zeros(n, dtype=np.uint32) if want_env_idx else None
+        envelopes = np.zeros((env_cap, 85), dtype=np.uint8)
+        n_env = np.zeros(2, dtype=np.uint32)
+        signers = np.zeros((env_cap, (self.n_keys + 63) // 64), dtype=np.uint64)
+        counts = np.zeros(env_cap, dtype=np.uint32)
+        check(self._lib.pbft_verify_frames_tally(
+            self._ctx, _ptr(buf), len(buf), _ptr(off), _ptr(flen), _ptr(peer) if peer is not None else None,
+            self.n_keys if n_replicas is None else n_replicas, n, env_cap, _ptr(out), _ptr(heads),
+            _ptr(env_idx) if want_env_idx else None, _ptr(envelopes), n_env.ctypes.data, _ptr(signers),
+            _ptr(counts)))
+        return out, heads, env_idx, envelopes, n_env, signers, counts
+
+    OPT_GROUP_SEED, OPT_GROUP_HASH_BITS = 16, 17
     OPT_SPLIT_BELOW, OPT_FINISH_WIDTH, OPT_KEY_TABLE_BUDGET_MB, OPT_FINISH_TREE, OPT_LAT_SPLIT = 1, 2, 3, 4, 5
     OPT_KERNEL_TIMING = 7
     OPT_FINISH_WAVES = 8
