@@ -415,6 +415,11 @@ int pbft_sign_batch(pbft_ctx *ctx, const uint8_t *seeds, uint32_t n_seeds, const
  * SIMD trade priorities so that they progress together (instead of oldest-first); 0: 4-wave blocks; any other
  * value (default; env PBFT_COMB_PRIO) = by batch size: 8-wave blocks where they fit one per CU (the 131k shard). */
 #define PBFT_OPT_COMB_PRIO 13
+/* 1: the 4-wave chain-form comb lowers each wave's issue priority as the wave progresses (3 through the hash, then
+ * 2, 1, 0 over thirds of the steps), so the waves sharing a SIMD close up and a launch's last waves end together
+ * instead of one by one; 0: off (oldest-first); any other value (default) = by batch size: on where a launch has
+ * more than two waves per SIMD.  Where PBFT_OPT_COMB_PRIO's 8-wave form is chosen, that form runs. */
+#define PBFT_OPT_COMB_BALANCE 18
 /* pbft_group_envelopes_device: the 64-bit seed of its row hash (default: drawn on the host at the context's first
  * grouping call).  The output does not depend on it. */
 #define PBFT_OPT_GROUP_SEED 16

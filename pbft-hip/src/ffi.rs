@@ -72,6 +72,7 @@ pub const PBFT_OPT_FINISH_WAVES: c_int = 8;
 pub const PBFT_OPT_COMB_PAIR: c_int = 10;
 pub const PBFT_OPT_FAULT_INJECT: c_int = 11;
 pub const PBFT_OPT_COMB_PRIO: c_int = 13;
+pub const PBFT_OPT_COMB_BALANCE: c_int = 18;
 pub const PBFT_MAX_REPLICA_CTX: u32 = 16;
 
 pub const PBFT_KIND_PREPREPARE: u8 = 0;

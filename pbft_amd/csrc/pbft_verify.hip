@@ -159,6 +159,8 @@ struct pbft_ctx {
   int comb_pair = -1;                  // comb_pair_kernel: 1 on, 0 off, -1 by batch size (PBFT_OPT_COMB_PAIR)
   int comb_prio = -1;                  // 8-wave comb blocks with paired wave priorities: 1, 0, -1 by batch size
                                        // (PBFT_OPT_COMB_PRIO)
+  int comb_balance = -1;               // 4-wave comb with priorities falling with each wave's progress: 1, 0, -1 by
+                                       // batch size (PBFT_OPT_COMB_BALANCE)
   int cus = 0;                         // compute units of the device
   // ev0 / ev1 around every launch (pbft_last_kernel_ms).  Off by default since r05: the two event records cost 7.5 us
   // per comb + finish pair, 4.5 % of the 131k shard (profiles/r05/shard/timing_events.txt)
@@ -558,6 +560,7 @@ static int launch_verify(pbft_ctx* c, const uint8_t* dR, const uint8_t* dS, cons
   a.pair = c->comb_pair;
   a.cus = c->cus;
   a.prio = c->comb_prio;
+  a.balance = c->comb_balance;
   a.wk = (PBFT_ENV_SCHED && dMI && msg_len == PBFT_ENVELOPE_LEN) ? dWK : nullptr;
   uint32_t* xyz = a.xyz;
   uint8_t* flags = a.flags;
@@ -1281,6 +1284,7 @@ int pbft_verify_ctx_clone(pbft_ctx* parent, pbft_ctx** out) {
   c->two_streams = parent->two_streams;
   c->comb_pair = parent->comb_pair;
   c->comb_prio = parent->comb_prio;
+  c->comb_balance = parent->comb_balance;
   c->key_budget_mb = parent->key_budget_mb;
   *out = c;
   return PBFT_OK;
@@ -2457,6 +2461,7 @@ int pbft_verify_set_option(pbft_ctx* c, int option, uint64_t value) {
     case PBFT_OPT_COMB_PAIR: c->comb_pair = value <= 1 ? (int)value : -1; return PBFT_OK;
     case PBFT_OPT_KEY_TABLE_BUDGET_MB: c->key_budget_mb = value; return PBFT_OK;
     case PBFT_OPT_COMB_PRIO: c->comb_prio = value <= 1 ? (int)value : -1; return PBFT_OK;
+    case PBFT_OPT_COMB_BALANCE: c->comb_balance = value <= 1 ? (int)value : -1; return PBFT_OK;
     case PBFT_OPT_FAULT_INJECT:
       if (value > 2) return set_err(PBFT_EINVAL, "fault injection point");
       c->fault_inject = (int)value;

@@ -251,8 +251,9 @@ __device__ __forceinline__ void sha512_k(uint32_t h[16], const uint32_t r[8], co
 // g_comb_stamp (a buffer no other code reads; read back by pbft_debug_comb_stamps in comb_pa13.hip, the 13-position
 // plan's translation unit).  Per wave: [0] s_memtime at start, [1] s_memrealtime at start, [2] s_memtime once the
 // hash, reduction and digit recoding are done, [3] shader cycles spent in the gathers' vmcnt(0) waits (summed over
-// the steps), [4] s_memtime at the end, [5] s_memrealtime at the end, [6] cycles in the steps' lgkmcnt(0) waits,
-// [7] the HW_ID register (SE / CU / SIMD of the wave).  VERDICT r04 item 3: attribute the 131k shard's stalls.
+// the steps; bits 32..63: the first step's share, i.e. the wait for the first table entry), [4] s_memtime at the
+// end, [5] s_memrealtime at the end, [6] cycles in the steps' lgkmcnt(0) waits, [7] the HW_ID register (SE / CU /
+// SIMD of the wave).  VERDICT r04 item 3: attribute the 131k shard's stalls.
 #ifndef PBFT_COMB_STAMPS
 #define PBFT_COMB_STAMPS 0
 #endif
@@ -270,7 +271,20 @@ static __device__ uint64_t g_comb_stamp[COMB_STAMP_WAVES][8];
 // round) one wave ran as fast as it runs alone (194k cycles, 105 us) and its partner finished ~55 us later on
 // its own, latency-bound (profiles/r05/spread/: lifetimes 193k vs 293k cycles on every SIMD).
 static constexpr uint32_t COMB_PRIO_LDS = 64;  // 8 progress words (+ pad) after the 8 entry buffers
-template <int LEN, class PLA, bool CHAIN = false, int WPB = 4>
+// BAL (PBFT_OPT_COMB_BALANCE): a wave's issue priority falls with its own progress -- 3 through the hash, the
+// reduction and the recoding, then 2, 1, 0 over thirds of the steps (four stretches of about equal VALU work; other
+// splits -- thirds moved earlier or later, three levels, top priority again for the last steps -- measured the
+// same or slower at 2^20, profiles/r07/comb_tiles/ab_schedules.txt).  No
+// wave looks at another: the SIMD's arbiter, oldest-first among equals, now serves the wave with the most work left.
+// Why: in a launch of several generations of blocks the oldest-first SIMD starves each new wave through its hash
+// (stamps at 2^20: 65 % of a wave's lifetime goes by before its first step) and drains the launch one wave at a
+// time -- 5.6 % of SIMD time with one wave resident, 5.9 % with two, 2.9 % with none while the slowest SIMD
+// finishes (profiles/r07/comb_tiles/attribution_parent.txt).  With BAL the waves of a SIMD close up on each other
+// and the last ones end together.
+#ifndef PBFT_COMB_BALANCE
+#define PBFT_COMB_BALANCE -1  // A/B: 1 / 0 force the default of PBFT_OPT_COMB_BALANCE on / off; -1 by batch size
+#endif
+template <int LEN, class PLA, bool CHAIN = false, int WPB = 4, bool BAL = false>
 __global__ void __launch_bounds__(64 * WPB, PBFT_COMB_WAVES_PER_EU) comb_kernel(
     const uint8_t* __restrict__ R, const uint8_t* __restrict__ S, const uint8_t* __restrict__ key_idx,
     uint32_t rs_stride, uint32_t k_stride,
@@ -291,6 +305,9 @@ __global__ void __launch_bounds__(64 * WPB, PBFT_COMB_WAVES_PER_EU) comb_kernel(
   typename ST::mask_t sgn = 0;        // bit j: digit of step j is negative
   bool s_ok, kok;
   constexpr bool PRIO = WPB == 8;
+  static_assert(!(PRIO && BAL), "the paired-priority form sets its priorities from its partner's progress");
+  constexpr int BAL_J1 = ST::N / 3, BAL_J2 = 2 * ST::N / 3;  // first steps at priority 1 and 0
+  if constexpr (BAL) __builtin_amdgcn_s_setprio(3);
   const uint32_t prog = (uint32_t)(uintptr_t)lds + WPB * COMB_LDS_PER_WAVE;  // PRIO: step count per wave
   if constexpr (PRIO) {
     if (lane == 0) lds_write32(prog + 4u * wave, 0u);
@@ -298,7 +315,7 @@ __global__ void __launch_bounds__(64 * WPB, PBFT_COMB_WAVES_PER_EU) comb_kernel(
   }
 #if PBFT_COMB_STAMPS
   const uint64_t st_t0 = COMB_T(), st_rt0 = COMB_RT();
-  uint64_t st_wait = 0, st_lgkm = 0, st_hash = 0;
+  uint64_t st_wait = 0, st_lgkm = 0, st_hash = 0, st_first = 0;
 #define COMB_WAIT_VM()                                  \
   do {                                                  \
     const uint64_t a_ = COMB_T();                       \
@@ -373,6 +390,7 @@ __global__ void __launch_bounds__(64 * WPB, PBFT_COMB_WAVES_PER_EU) comb_kernel(
   const uint8_t* tB = (const uint8_t*)tabB;
   const uint8_t* tA = (const uint8_t*)tabA;
   const uint32_t rd0 = ebuf + 128u * lane + 16u * (lane & 7);  // logical byte o of my entry at rd0 ^ o
+  if constexpr (BAL) __builtin_amdgcn_s_setprio(2);
   // (each lane re-reads only the indices it wrote itself: no barrier needed)
   dma_entry_lines(ST::is_a(0) ? tA : tB, eidx[i], lane, ebuf);
   uint32_t nidx = eidx[Npad + i];
@@ -382,6 +400,9 @@ __global__ void __launch_bounds__(64 * WPB, PBFT_COMB_WAVES_PER_EU) comb_kernel(
     fe qa, qb, k;
     const bool neg = (uint32_t)sgn & 1u;
     COMB_WAIT_VM();
+#if PBFT_COMB_STAMPS
+    st_first = st_wait;
+#endif
     lds_entry_signed(rd0, neg, qa, qb, k);
     COMB_WAIT_LGKM();  // lgkmcnt(0): entry in VGPRs before the DMA reuses the buffer
     dma_entry_lines(ST::is_a(1) ? tA : tB, nidx, lane, ebuf);
@@ -395,6 +416,10 @@ __global__ void __launch_bounds__(64 * WPB, PBFT_COMB_WAVES_PER_EU) comb_kernel(
     if constexpr (PRIO) {
       if (lane == 0) lds_write32(prog + 4u * wave, (uint32_t)j);
       partner = lds_read32(prog + 4u * (wave ^ 4u));
+    }
+    if constexpr (BAL) {
+      if (j == BAL_J1) __builtin_amdgcn_s_setprio(1);
+      else if (j == BAL_J2) __builtin_amdgcn_s_setprio(0);
     }
     COMB_WAIT_VM();
     lds_entry_signed(rd0, neg, qa, qb, k);
@@ -439,7 +464,11 @@ __global__ void __launch_bounds__(64 * WPB, PBFT_COMB_WAVES_PER_EU) comb_kernel(
     const uint64_t gw = (uint64_t)blockIdx.x * WPB + wave;
     if (lane == 0 && gw < COMB_STAMP_WAVES) {
       uint64_t* o = g_comb_stamp[gw];
-      o[0] = st_t0; o[1] = st_rt0; o[2] = st_hash; o[3] = st_wait; o[4] = t_end; o[5] = rt_end; o[6] = st_lgkm;
+      // all 8 words of the row are taken (o[7]: HW_ID), so o[3] packs two cycle counts, each far below 2^32:
+      // bits 0..31 the vmcnt waits of all steps, bits 32..63 the first step's share (tools/comb_stamps.py unpacks)
+      o[0] = st_t0; o[1] = st_rt0; o[2] = st_hash;
+      o[3] = (st_wait & 0xFFFFFFFFu) | (st_first << 32);
+      o[4] = t_end; o[5] = rt_end; o[6] = st_lgkm;
       o[7] = (uint64_t)__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11)) |       // HW_ID (hwreg 4)
              ((uint64_t)__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11)) << 32);  // XCC_ID (hwreg 20)
     }
@@ -1020,6 +1049,8 @@ struct comb_launch_args {
   int cus = 0;             // compute units of the device (0: unknown)
   int prio = -1;           // one-lane chain-form comb: 8-wave blocks with paired wave priorities (WPB = 8): 1 on,
                            // 0 off, -1 by batch size
+  int balance = -1;        // 4-wave chain-form comb: priority falling with a wave's progress (BAL): 1 on, 0 off, -1 by
+                           // batch size
   hipStream_t st;
 };
 
@@ -1052,6 +1083,14 @@ static inline bool comb_chain(const comb_launch_args& a) {
 static inline bool comb_chain_prio(const comb_launch_args& a) {
   return comb_chain(a) &&
          (a.prio >= 0 ? a.prio > 0 : (a.cus > 0 && (a.N + 2 * BLOCK - 1) / (2 * BLOCK) <= (uint64_t)a.cus));
+}
+// ... with priorities that fall with each wave's progress (comb_kernel BAL): by size, where the launch has more
+// than 2 waves per SIMD (cus x 8 waves: past the range of the paired form above), i.e. where the oldest-first SIMD
+// drains the launch wave by wave.  Measured from 140,000 signatures to 2^20 in profiles/r07/comb_tiles/ab.txt.
+static inline bool comb_chain_balance(const comb_launch_args& a) {
+  const int sel = a.balance >= 0 ? a.balance : PBFT_COMB_BALANCE;
+  return comb_chain(a) && !comb_chain_prio(a) &&
+         (sel >= 0 ? sel > 0 : (a.cus > 0 && (a.N + 63) / 64 > (uint64_t)a.cus * 8));
 }
 // Launch the comb (or, in latency mode, the 4-lanes-per-signature kernel) for
 // key plan PLA; LEN 85 (the signed envelope) is a specialised template.
@@ -1096,6 +1135,11 @@ hipError_t launch_comb_plan(const comb_launch_args& a) {
                          a.st, a.R, a.S, a.K, a.rs_stride, a.k_stride, a.M, a.msg_len, a.msg_stride, N, Npad2, a.tabB,
                          a.tabA, a.keys, a.key_ok, a.n_keys, a.xyz, a.flags, a.eidx, a.msg_idx, a.n_msg, a.mi_stride,
                          a.wk);
+    } else if (comb_chain_balance(a)) {
+      hipLaunchKernelGGL((comb_kernel<PBFT_ENVELOPE_LEN, PLA, true, 4, true>), dim3((unsigned)blocks), dim3(BLOCK),
+                         lds, a.st, a.R, a.S, a.K, a.rs_stride, a.k_stride, a.M, a.msg_len, a.msg_stride, N, Npad,
+                         a.tabB, a.tabA, a.keys, a.key_ok, a.n_keys, a.xyz, a.flags, a.eidx, a.msg_idx, a.n_msg,
+                         a.mi_stride, a.wk);
     } else if (comb_chain(a)) {
       hipLaunchKernelGGL((comb_kernel<PBFT_ENVELOPE_LEN, PLA, true, 4>), dim3((unsigned)blocks), dim3(BLOCK), lds,
                          a.st, a.R, a.S, a.K, a.rs_stride, a.k_stride, a.M, a.msg_len, a.msg_stride, N, Npad, a.tabB,

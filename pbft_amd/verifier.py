@@ -488,6 +488,7 @@ class GpuBatchVerifier:
     OPT_COMB_PAIR = 10
     OPT_FAULT_INJECT = 11
     OPT_COMB_PRIO = 13
+    OPT_COMB_BALANCE = 18
 
     def set_option(self, option: int, value: int) -> None:
         """pbft_verify_set_option: latency-mode threshold, finish width, key-table budget (include/pbft_verify.h)."""

@@ -5,7 +5,9 @@
 Per size: the in-kernel clock (delta s_memtime / delta s_memrealtime x 100 MHz, median over waves), and per wave the
 shader cycles of its phases -- hash + recoding, gather waits (vmcnt(0) before each step's entry read), LDS waits
 (lgkmcnt(0)), the rest of the steps (arithmetic) -- plus the spread of wave start / end times across the launch
-(realtime, so comparable across CUs) and the waves per SIMD that were live.
+(realtime, so comparable across CUs) and the waves per SIMD that were live.  Then the attribution of the time in which
+a SIMD has fewer than 4 waves resident (a sweep over each SIMD's wave intervals) and of each wave's time from its
+start to its first table entry (hash + recoding, then the first gather's vmcnt wait), both as shares of the launch.
 usage: python tools/comb_stamps.py build/ab/libpbft_stamps.so [sizes...]"""
 import ctypes
 import os
@@ -44,12 +46,15 @@ def main():
         waves = (n + 63) // 64
         buf = np.zeros((min(waves, 16384), 8), np.uint64)
         assert lib.pbft_debug_comb_stamps(buf.ctypes.data, len(buf)) == 0
+        if os.environ.get("PBFT_STAMPS_DUMP"):  # the raw stamps, for other analyses
+            np.save(os.path.join(os.environ["PBFT_STAMPS_DUMP"], f"comb_stamps_{n}.npy"), buf)
         b = buf.astype(np.float64)
         life = b[:, 4] - b[:, 0]
         rt = (b[:, 5] - b[:, 1])
         clk = np.median(life / np.maximum(rt, 1)) * 0.1  # GHz (realtime ticks at 100 MHz)
         hash_ = b[:, 2] - b[:, 0]
-        wait = b[:, 3]
+        wait = (buf[:, 3] & np.uint64(0xFFFFFFFF)).astype(np.float64)
+        first = (buf[:, 3] >> np.uint64(32)).astype(np.float64)  # the first step's share of the vmcnt waits
         lgkm = b[:, 6]
         rest = life - hash_ - wait - lgkm
         t0 = b[:, 1].min()
@@ -88,7 +93,67 @@ def main():
         print(f"  live waves over the launch (200 samples): max {live.max()}, mean {live.mean():.0f} "
               f"(= {live.mean() / 1024:.2f} per SIMD), quartiles of time: "
               + " ".join(f"{live[i * 50:(i + 1) * 50].mean():.0f}" for i in range(4)))
+        attribution(buf, sid, clk)
     v.close()
+
+
+def attribution(buf, sid, clk):
+    """Per SIMD: the time of the launch with k < 4 waves resident (realtime ticks of 10 ns, the launch taken from the
+    first wave start to the last wave end of the chip), split into the lead-in before the SIMD's first wave, the gaps
+    between its first start and its last end, and the tail after its last wave; and per wave the start-to-first-entry
+    exposure."""
+    s0 = buf[:, 1].astype(np.int64)
+    s1 = buf[:, 5].astype(np.int64)
+    t_lo, t_hi = s0.min(), s1.max()
+    span = float(t_hi - t_lo)
+    lead, mid, tail, occ = [], [], [], np.zeros(5)
+    for u in np.unique(sid):
+        m = sid == u
+        ev = sorted([(int(t), 1) for t in s0[m]] + [(int(t), -1) for t in s1[m]])
+        a, b = int(s0[m].min()), int(s1[m].max())
+        n, prev, short_mid = 0, a, 0
+        occ[0] += (a - t_lo) + (t_hi - b)
+        for t, d in ev:
+            occ[min(n, 4)] += t - prev
+            if n < 4:
+                short_mid += (t - prev) * (4 - n) / 4.0  # wave slots empty, as a share of the SIMD's 4
+            n, prev = n + d, t
+        lead.append(a - t_lo)
+        tail.append(t_hi - b)
+        mid.append(short_mid)
+    ns = len(lead)
+    lead, mid, tail = np.array(lead, float), np.array(mid, float), np.array(tail, float)
+    print(f"  attribution over {ns} SIMDs, launch span {span / 100:.1f} us (10-ns ticks):")
+    print("    SIMD time by resident waves: " + "  ".join(f"{k}:{100 * occ[k] / (ns * span):5.2f} %" for k in range(5)))
+    print(f"    fewer than 4 resident: {100 * occ[:4].sum() / (ns * span):.2f} % of SIMD time "
+          f"(mean {occ[:4].sum() / ns / 100:.1f} us per SIMD)")
+    for name, x in (("lead-in before the SIMD's first wave", lead), ("tail after its last wave", tail),
+                    ("empty slots between (slot-weighted)", mid)):
+        print(f"    {name:38s} mean {x.mean() / 100:6.2f} us  p90 {np.percentile(x, 90) / 100:6.2f}  max "
+              f"{x.max() / 100:6.2f}  ({100 * x.mean() / span:5.2f} % of the span)")
+    b = buf.astype(np.float64)
+    hash_ = b[:, 2] - b[:, 0]
+    first = (buf[:, 3] >> np.uint64(32)).astype(np.float64)
+    life = b[:, 4] - b[:, 0]
+    to_entry = hash_ + first
+    per_simd_waves = len(buf) / ns
+    for name, x in (("start -> indices recoded (hash phase)", hash_), ("first gather vmcnt wait", first),
+                    ("start -> first entry in registers", to_entry)):
+        us = x / (clk * 1e3)
+        print(f"    {name:38s} mean {x.mean():8.0f} cyc = {us.mean():6.2f} us  p90 {np.percentile(us, 90):6.2f} us  "
+              f"({100 * x.mean() / life.mean():5.2f} % of a wave's lifetime; x {per_simd_waves:.0f} waves per SIMD / 4 "
+              f"slots = {100 * us.mean() * per_simd_waves / 4 / (span / 100):5.2f} % of the span)")
+    # waves of a SIMD that start within 2 us of another wave of the same SIMD: their front ends coincide
+    co = 0
+    for u in np.unique(sid):
+        t = np.sort(s0[sid == u])
+        d = np.diff(t)
+        near = np.zeros(len(t), bool)
+        near[1:] |= d < 200
+        near[:-1] |= d < 200
+        co += int(near.sum())
+    print(f"    waves starting within 2 us of another wave of their SIMD: {co} of {len(buf)} "
+          f"({100 * co / len(buf):.1f} %)")
 
 
 if __name__ == "__main__":
