@@ -426,6 +426,10 @@ int pbft_sign_batch(pbft_ctx *ctx, const uint8_t *seeds, uint32_t n_seeds, const
 /* Testing: keep only the low b bits of the row hash (0..64; default 64).  b = 0 sends every row down one probe
  * chain; the output does not change, the time does. */
 #define PBFT_OPT_GROUP_HASH_BITS 17
+/* Testing: the tile bytes of pbft_wire_index_streams_device (include/pbft_wire.h): a power of two from 512 to the
+ * default, 16384; 0 restores the default; anything else is PBFT_EINVAL.  The output does not depend on it; the
+ * workspace does, so set it before pbft_index_reserve. */
+#define PBFT_OPT_INDEX_TILE 19
 int pbft_verify_set_option(pbft_ctx *ctx, int option, uint64_t value);
 
 /* Diagnostics */

@@ -214,6 +214,75 @@ int pbft_verify_frames_tally(pbft_ctx *ctx, const uint8_t *stream, uint64_t stre
                              uint32_t *env_idx_out, uint8_t *envelopes_out, uint32_t *n_env_out,
                              uint64_t *signers_out, uint32_t *count_out);
 
+/* ---- Connection streams in: the frame index made on the device (kernels: pbft_amd/csrc/wire_index.hip) ----
+ * What upgrade_inbound has is one buffer of bytes per authenticated connection.  Here they are S segments of one
+ * stream: segment s = bytes [seg_off[s], seg_off[s] + seg_len[s]) at any alignment, with gaps between segments as
+ * they come; it begins at a frame boundary and may end inside a varint or a body.  For every segment the device
+ * computes what pbft_wire_frame_index(stream + seg_off[s], seg_len[s], unlimited, ...) computes, value for value: the
+ * same frames, the same flen, off shifted by seg_off[s] (an absolute body offset, as
+ * pbft_wire_decode_frames_device consumes it), the same consumed, and "framing error" exactly where that function
+ * returns PBFT_EINVAL (the frames in front of the error are delivered).  Frames are numbered by segment, then by
+ * position in the segment; peer[f] is its segment's peer.  No byte outside a segment influences its result. */
+typedef struct {
+  uint64_t consumed; /* bytes of whole frames, counted from seg_off[s] */
+  uint32_t first;    /* number of the segment's first frame = the frames of the segments in front of it */
+  uint32_t n_frames;
+  uint32_t status;   /* PBFT_SEG_* */
+  uint32_t pad;      /* 0 */
+} pbft_seg_head;
+#define PBFT_SEG_OK 0
+#define PBFT_SEG_EFRAMING 1 /* framing error at consumed (pbft_wire_frame_index: PBFT_EINVAL) */
+/* The segment is not read, n_frames = consumed = 0: it does not lie inside stream_bytes, or the lengths of the
+ * segments up to and including it that do lie inside add up to more than stream_bytes (segments that overlap). */
+#define PBFT_SEG_EOUTSIDE 2
+
+/* Device, enqueue only (kernel nodes on one stream: no allocation, copy, memset or synchronisation, no lane waits for
+ * another block; capturable after pbft_index_reserve).  d_stream as for pbft_wire_decode_frames_device: 16-byte
+ * aligned, readable up to stream_bytes rounded up to 16, and only 16-byte granules of that range are read.
+ * d_seg_peer: NULL or one authenticated replica index per segment; d_peer must be NULL iff it is.
+ * Outputs: d_off / d_len / d_peer [frame_cap]; frames numbered >= frame_cap are not written and are counted in
+ * d_n_frames[1] (later frames are lost, none is miscounted); entries [min(total, frame_cap), frame_cap) are padding:
+ * off 0, len 0, peer 0xFFFF, which the decoder marks PBFT_WIRE_EDEFER without reading and the grouping skips, so the
+ * whole chain can be enqueued with N = frame_cap.  d_seg_heads [S] is complete whatever frame_cap is.
+ * d_n_frames [2] = {total, not written}.  S = 0 or frame_cap = 0 is legal.
+ * PBFT_EINVAL: a null pointer that would be used or a misaligned one, S > 65536, frame_cap > 2^31, stream_bytes >
+ * 2^31; a refused call has enqueued nothing.  The workspace (tile tables: ~0.19 bytes per stream byte at the default
+ * tile, plus ~3 KB per segment) grows on first use of a larger call, which is then not capturable. */
+int pbft_wire_index_streams_device(pbft_ctx *ctx, const uint8_t *d_stream, uint64_t stream_bytes,
+                                   const uint64_t *d_seg_off, const uint64_t *d_seg_len, const uint16_t *d_seg_peer,
+                                   uint32_t S, uint64_t frame_cap, uint64_t *d_off, uint32_t *d_len, uint16_t *d_peer,
+                                   pbft_seg_head *d_seg_heads, uint32_t *d_n_frames, void *stream);
+
+/* Pre-size the index workspace for calls of up to max_stream_bytes and max_segments at the current tile size
+ * (PBFT_OPT_INDEX_TILE): required before a capture. */
+int pbft_index_reserve(pbft_ctx *ctx, uint64_t max_stream_bytes, uint32_t max_segments);
+
+/* Device, enqueue only, one stream: the index, then pbft_verify_frames_tally_device with N = frame_cap over the
+ * index it wrote.  Every buffer is the caller's, as for that function; the per-frame and per-envelope outputs are
+ * word for word what it writes when handed the same padded index.  Call pbft_verify_reserve(frame_cap),
+ * pbft_group_reserve(frame_cap) and pbft_index_reserve before a capture.  Argument checks of both functions, all in
+ * front of the first launch. */
+int pbft_verify_streams_tally_device(pbft_ctx *ctx, const uint8_t *d_stream, uint64_t stream_bytes,
+                                     const uint64_t *d_seg_off, const uint64_t *d_seg_len, const uint16_t *d_seg_peer,
+                                     uint32_t S, uint32_t n_replicas, uint64_t frame_cap, uint64_t *d_off,
+                                     uint32_t *d_len, uint16_t *d_peer, pbft_seg_head *d_seg_heads,
+                                     uint32_t *d_n_frames, uint8_t *d_records, pbft_frame_head *d_heads,
+                                     uint64_t *d_bitmap, uint32_t env_cap, uint32_t *d_env_idx, uint8_t *d_envelopes,
+                                     uint32_t *d_n_env, uint64_t *d_signers, uint32_t *d_count, void *stream);
+
+/* Host, blocking: the stream and the segment table go up, the index is made on the device, the totals and the segment
+ * heads come back; then the front half of pbft_verify_frames_tally runs on N = min(total, frame_cap) frames with the
+ * index where it is (it comes back only if a frame is PBFT_WIRE_EDEFER, for the host parser, or if off_out /
+ * flen_out are not NULL), then group, verify and tally.  Outputs as pbft_verify_frames_tally (the per-frame ones hold
+ * frame_cap entries, N are written) plus seg_heads_out [S], n_frames_out [2] and, unless NULL, off_out / flen_out
+ * [frame_cap]: equal to that function fed with the host index of every segment and a per-frame peer array. */
+int pbft_verify_streams_tally(pbft_ctx *ctx, const uint8_t *stream, uint64_t stream_bytes, const uint64_t *seg_off,
+                              const uint64_t *seg_len, const uint16_t *seg_peer, uint32_t S, uint32_t n_replicas,
+                              uint64_t frame_cap, uint32_t env_cap, uint64_t *bitmap_out, pbft_frame_head *heads_out,
+                              uint32_t *env_idx_out, uint8_t *envelopes_out, uint32_t *n_env_out,
+                              uint64_t *signers_out, uint32_t *count_out, pbft_seg_head *seg_heads_out,
+                              uint32_t *n_frames_out, uint64_t *off_out, uint32_t *flen_out);
+
 #ifdef __cplusplus
 }
 #endif

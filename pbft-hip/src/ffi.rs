@@ -45,6 +45,20 @@ pub struct pbft_frame_head {
     pub frame_len: u32,
 }
 
+/// Head of one connection segment (pbft_wire_index_streams_device / pbft_verify_streams_tally): 24 bytes.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct pbft_seg_head {
+    pub consumed: u64,
+    pub first: u32,
+    pub n_frames: u32,
+    pub status: u32,
+    pub pad: u32,
+}
+pub const PBFT_SEG_OK: u32 = 0;
+pub const PBFT_SEG_EFRAMING: u32 = 1;
+pub const PBFT_SEG_EOUTSIDE: u32 = 2;
+
 pub const PBFT_WIRE_OK: u8 = 0;
 pub const PBFT_WIRE_EDEFER: u8 = 6;
 pub const PBFT_FRAME_MIN: u32 = 336;
@@ -73,6 +87,7 @@ pub const PBFT_OPT_COMB_PAIR: c_int = 10;
 pub const PBFT_OPT_FAULT_INJECT: c_int = 11;
 pub const PBFT_OPT_COMB_PRIO: c_int = 13;
 pub const PBFT_OPT_COMB_BALANCE: c_int = 18;
+pub const PBFT_OPT_INDEX_TILE: c_int = 19;
 pub const PBFT_MAX_REPLICA_CTX: u32 = 16;
 
 pub const PBFT_KIND_PREPREPARE: u8 = 0;
@@ -358,4 +373,25 @@ extern "C" {
                                     bitmap_out: *mut u64, heads_out: *mut pbft_frame_head, env_idx_out: *mut u32,
                                     envelopes_out: *mut u8, n_env_out: *mut u32, signers_out: *mut u64,
                                     count_out: *mut u32) -> c_int;
+    pub fn pbft_wire_index_streams_device(ctx: *mut pbft_ctx, d_stream: *const u8, stream_bytes: u64,
+                                          d_seg_off: *const u64, d_seg_len: *const u64, d_seg_peer: *const u16,
+                                          n_segments: u32, frame_cap: u64, d_off: *mut u64, d_len: *mut u32,
+                                          d_peer: *mut u16, d_seg_heads: *mut pbft_seg_head, d_n_frames: *mut u32,
+                                          stream: *mut c_void) -> c_int;
+    pub fn pbft_index_reserve(ctx: *mut pbft_ctx, max_stream_bytes: u64, max_segments: u32) -> c_int;
+    pub fn pbft_verify_streams_tally_device(ctx: *mut pbft_ctx, d_stream: *const u8, stream_bytes: u64,
+                                            d_seg_off: *const u64, d_seg_len: *const u64, d_seg_peer: *const u16,
+                                            n_segments: u32, n_replicas: u32, frame_cap: u64, d_off: *mut u64,
+                                            d_len: *mut u32, d_peer: *mut u16, d_seg_heads: *mut pbft_seg_head,
+                                            d_n_frames: *mut u32, d_records: *mut u8,
+                                            d_heads: *mut pbft_frame_head, d_bitmap: *mut u64, env_cap: u32,
+                                            d_env_idx: *mut u32, d_envelopes: *mut u8, d_n_env: *mut u32,
+                                            d_signers: *mut u64, d_count: *mut u32, stream: *mut c_void) -> c_int;
+    pub fn pbft_verify_streams_tally(ctx: *mut pbft_ctx, stream: *const u8, stream_bytes: u64, seg_off: *const u64,
+                                     seg_len: *const u64, seg_peer: *const u16, n_segments: u32, n_replicas: u32,
+                                     frame_cap: u64, env_cap: u32, bitmap_out: *mut u64,
+                                     heads_out: *mut pbft_frame_head, env_idx_out: *mut u32, envelopes_out: *mut u8,
+                                     n_env_out: *mut u32, signers_out: *mut u64, count_out: *mut u32,
+                                     seg_heads_out: *mut pbft_seg_head, n_frames_out: *mut u32, off_out: *mut u64,
+                                     flen_out: *mut u32) -> c_int;
 }

@@ -202,6 +202,27 @@ pub struct FramesTally {
     pub consumed: usize,
 }
 
+/// Head of one connection segment (ffi::pbft_seg_head): frames, bytes consumed, framing status.
+pub type SegHead = ffi::pbft_seg_head;
+
+/// Result of `GpuVerifier::verify_streams_tally`: `FramesTally` over the frames of every connection, numbered by
+/// connection and then by position, plus one head per connection.
+#[derive(Clone, Debug)]
+pub struct StreamsTally {
+    pub bitmap: Bitmap,
+    pub heads: Vec<FrameHead>,
+    pub envelopes: Vec<[u8; 85]>,
+    pub tally: Tally,
+    pub envelopes_found: u32,
+    pub rows_lost: u32,
+    /// Per connection: `first` (number of its first frame), `n_frames`, `consumed` and `status`.
+    pub segments: Vec<SegHead>,
+    /// Whole frames in all connections (may exceed frame_cap).
+    pub frames_found: u32,
+    /// Frames numbered >= frame_cap: not decoded, not verified.
+    pub frames_lost: u32,
+}
+
 /// Handle of one submitted batch.
 #[derive(Debug, PartialEq, Eq)]
 pub struct Ticket(pub u64);
@@ -353,6 +374,57 @@ impl GpuVerifier {
         tally.counts.truncate(kept);
         Ok(FramesTally { bitmap, heads, envelopes, tally, envelopes_found: n_env[0], rows_lost: n_env[1],
                          consumed: used as usize })
+    }
+    /// `verify_frames_tally` of what `upgrade_inbound` has: one buffer of bytes per authenticated connection, each
+    /// with its peer's replica index (pbft_verify_streams_tally).  The buffers are laid end to end (each at a 16-byte
+    /// boundary) into one stream; the varint walk, the decode, the grouping, the verify and the tally all run on the
+    /// GPU.  Frames are numbered by connection, then by position.  `frame_cap`: room for that many frames -- later
+    /// ones are not verified (`frames_lost`).  `segments[i]`: what connection i consumed, how many frames it had and
+    /// whether its framing broke (status PBFT_SEG_EFRAMING at `consumed`: close that connection).
+    pub fn verify_streams_tally(&mut self, conns: &[(&[u8], u16)], n_replicas: u32, frame_cap: usize,
+                                env_cap: u32) -> Result<StreamsTally> {
+        if self.inflight.is_some() {
+            return Err(Error { code: ffi::PBFT_EBUSY, message: "one batch in flight per context".into() });
+        }
+        let (mut wb, mut wa, mut n_keys) = (0u32, 0u32, 0u32);
+        check(unsafe { ffi::pbft_verify_ctx_info(self.ctx, &mut wb, &mut wa, &mut n_keys) })?;
+        let mut stream: Vec<u8> = Vec::new();
+        let (mut seg_off, mut seg_len, mut seg_peer) = (Vec::new(), Vec::new(), Vec::new());
+        for (bytes, peer) in conns {
+            stream.resize((stream.len() + 15) & !15, 0);
+            seg_off.push(stream.len() as u64);
+            seg_len.push(bytes.len() as u64);
+            seg_peer.push(*peer);
+            stream.extend_from_slice(bytes);
+        }
+        let words_per_env = (n_keys as usize + 63) / 64;
+        let cap_env = env_cap as usize;
+        let mut bitmap = Bitmap::zeros(frame_cap);
+        let mut heads = vec![FrameHead::default(); frame_cap];
+        let mut envelopes = vec![[0u8; 85]; cap_env];
+        let mut n_env = [0u32; 2];
+        let mut n_frames = [0u32; 2];
+        let mut segments = vec![SegHead::default(); conns.len()];
+        let mut tally = Tally { signers: vec![0u64; cap_env * words_per_env], counts: vec![0u32; cap_env],
+                                words_per_env };
+        check(unsafe {
+            ffi::pbft_verify_streams_tally(self.ctx, stream.as_ptr(), stream.len() as u64, seg_off.as_ptr(),
+                                           seg_len.as_ptr(), seg_peer.as_ptr(), conns.len() as u32, n_replicas,
+                                           frame_cap as u64, env_cap, bitmap.0.as_mut_ptr(), heads.as_mut_ptr(),
+                                           ptr::null_mut(), envelopes.as_mut_ptr() as *mut u8, n_env.as_mut_ptr(),
+                                           tally.signers.as_mut_ptr(), tally.counts.as_mut_ptr(),
+                                           segments.as_mut_ptr(), n_frames.as_mut_ptr(), ptr::null_mut(),
+                                           ptr::null_mut())
+        })?;
+        let n = (n_frames[0] as usize).min(frame_cap);
+        heads.truncate(n);
+        bitmap.0.truncate((n + 63) / 64);
+        let kept = (n_env[0] as usize).min(cap_env);
+        envelopes.truncate(kept);
+        tally.signers.truncate(kept * words_per_env);
+        tally.counts.truncate(kept);
+        Ok(StreamsTally { bitmap, heads, envelopes, tally, envelopes_found: n_env[0], rows_lost: n_env[1], segments,
+                          frames_found: n_frames[0], frames_lost: n_frames[1] })
     }
     /// Another context on the same GPU sharing this one's tables (own HIP stream).
     pub fn try_clone(&self) -> Result<Self> {

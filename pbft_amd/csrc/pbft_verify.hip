@@ -37,6 +37,7 @@ using namespace pbft;
 #include "tally_kernels.h"
 #include "group_kernels.h"
 #include "wire_decode_kernels.h"
+#include "wire_index_kernels.h"
 // Finish configuration by batch size (signatures per lane, product tree, waves per SIMD), measured on MI355X
 // with the lane-parallel wave inversion (profiles/r03/ab_finish.txt): 131k 0.2115 -> 0.1906 ms (width 2),
 // 262k 0.3628 -> 0.3429 (width 4), 2^20 finish kernel 118.6 -> 91.4 us (width 8, tree, 2 waves per SIMD).
@@ -249,6 +250,11 @@ struct pbft_ctx {
   uint64_t group_seed = 0;
   bool group_seeded = false;
   uint32_t group_hash_bits = 64;
+  // pbft_wire_index_streams_device: tables and starts (grow-only; pbft_index_reserve) and the tile bytes
+  // (PBFT_OPT_INDEX_TILE)
+  uint8_t* d_index = nullptr;
+  size_t index_cap = 0;  // bytes
+  uint32_t index_tile = INDEX_TILE_DEFAULT;
 };
 
 #ifndef PBFT_ENV_SCHED
@@ -1029,6 +1035,7 @@ int pbft_verify_ctx_destroy(pbft_ctx* c) {
   (void)hipFree(c->d_tally);
   (void)hipFree(c->d_fpatch);
   (void)hipFree(c->d_group);
+  (void)hipFree(c->d_index);
   if (c->h_bitmap) (void)hipHostFree(c->h_bitmap);
   if (c->h_stage) (void)hipHostFree(c->h_stage);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -2142,6 +2149,10 @@ static int check_host_frames_args(pbft_ctx* c, const uint8_t* stream, uint64_t s
   return PBFT_OK;
 }
 
+static int frames_settle(pbft_ctx* c, const uint8_t* stream, const uint64_t* off, const uint32_t* flen,
+                         const uint16_t* peer, uint32_t n_replicas, uint64_t N, pbft_frame_head* heads_out,
+                         uint8_t* d, pbft_frame_head* d_heads);
+
 // The front half of the host forms, N > 0: stream and index into the device staging (laid out by `lay`, with `extra`
 // bytes behind it for the caller), the decode, the heads back, the host's word on every deferred frame, and the
 // patch of those that became OK.  Returns with all N records and heads settled on the device and the stream idle.
@@ -2163,6 +2174,14 @@ static int frames_stage_decode(pbft_ctx* c, const uint8_t* stream, uint64_t stre
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(heads_out, d_heads, sizeof(pbft_frame_head) * N, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  return frames_settle(c, stream, off, flen, peer, n_replicas, N, heads_out, d, d_heads);
+}
+
+// The host's word on every frame the device deferred (heads_out holds the device's heads; off / flen / peer are
+// read for those frames only), and the patch of those that became OK into the N records at d and heads at d_heads.
+static int frames_settle(pbft_ctx* c, const uint8_t* stream, const uint64_t* off, const uint32_t* flen,
+                         const uint16_t* peer, uint32_t n_replicas, uint64_t N, pbft_frame_head* heads_out,
+                         uint8_t* d, pbft_frame_head* d_heads) {
   // the frames the device deferred: the general parser, and the status rules of pbft_wire_decode_votes
   std::vector<uint32_t> pidx;
   std::vector<uint8_t> prec;
@@ -2327,6 +2346,213 @@ int pbft_verify_frames_tally(pbft_ctx* c, const uint8_t* stream, uint64_t stream
   return PBFT_OK;
 }
 
+// ---- connection streams in: the frame index made on the device (include/pbft_wire.h; kernels: wire_index.hip) ----
+static_assert(sizeof(pbft_seg_head) == 24, "pbft_seg_head is 24 bytes");
+static int ensure_index(pbft_ctx* c, uint64_t stream_bytes, uint32_t S) {
+  const size_t bytes = index_ws(stream_bytes, S, c->index_tile).total;
+  if (bytes <= c->index_cap) return PBFT_OK;
+  if (c->d_index) HIP_TRY(hipFree(c->d_index));  // (waits for the device: an earlier call may still use it)
+  c->d_index = nullptr;
+  c->index_cap = 0;
+  if (hipMalloc(&c->d_index, bytes) != hipSuccess) return set_err(PBFT_ENOMEM, "index workspace alloc");
+  c->index_cap = bytes;
+  return PBFT_OK;
+}
+
+static int check_index_args(const void* d_stream, uint64_t stream_bytes, const void* d_seg_off, const void* d_seg_len,
+                            const void* d_seg_peer, uint64_t S, uint64_t frame_cap, const void* d_off,
+                            const void* d_len, const void* d_peer, const void* d_seg_heads, const void* d_n_frames) {
+  if (S > pbft::IX_MAX_SEGMENTS) return set_err(PBFT_EINVAL, "more than 65536 segments");
+  if (frame_cap > ((uint64_t)1 << 31)) return set_err(PBFT_EINVAL, "frame_cap above 2^31");
+  if (stream_bytes > pbft::IX_MAX_STREAM) return set_err(PBFT_EINVAL, "more than 2^31 stream bytes to index");
+  if (!d_n_frames || (stream_bytes && !d_stream) || (S && (!d_seg_off || !d_seg_len || !d_seg_heads)) ||
+      (frame_cap && (!d_off || !d_len)) || (frame_cap && S && !d_peer != !d_seg_peer))
+    return set_err(PBFT_EINVAL, "null index argument");
+  if (((uintptr_t)d_stream & 15) || ((uintptr_t)d_seg_off & 7) || ((uintptr_t)d_seg_len & 7) ||
+      ((uintptr_t)d_seg_peer & 1) || ((uintptr_t)d_off & 7) || ((uintptr_t)d_len & 3) || ((uintptr_t)d_peer & 1) ||
+      ((uintptr_t)d_seg_heads & 7) || ((uintptr_t)d_n_frames & 3))
+    return set_err(PBFT_EINVAL, "misaligned index pointer");
+  return PBFT_OK;
+}
+
+int pbft_wire_index_streams_device(pbft_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes,
+                                   const uint64_t* d_seg_off, const uint64_t* d_seg_len, const uint16_t* d_seg_peer,
+                                   uint32_t S, uint64_t frame_cap, uint64_t* d_off, uint32_t* d_len, uint16_t* d_peer,
+                                   pbft_seg_head* d_seg_heads, uint32_t* d_n_frames, void* stream) {
+  if (!c) return set_err(PBFT_EINVAL, "null context");
+  int rc = check_index_args(d_stream, stream_bytes, d_seg_off, d_seg_len, d_seg_peer, S, frame_cap, d_off, d_len,
+                            d_peer, d_seg_heads, d_n_frames);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  rc = ensure_index(c, stream_bytes, S);
+  if (rc) return rc;
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  HIP_TRY(launch_index_streams(d_stream, stream_bytes, d_seg_off, d_seg_len, d_seg_peer, S, frame_cap, c->index_tile,
+                               c->d_index, d_off, d_len, frame_cap ? d_peer : nullptr, d_seg_heads, d_n_frames, st));
+  return PBFT_OK;
+}
+
+int pbft_index_reserve(pbft_ctx* c, uint64_t max_stream_bytes, uint32_t max_segments) {
+  if (!c) return set_err(PBFT_EINVAL, "null context");
+  if (max_segments > pbft::IX_MAX_SEGMENTS) return set_err(PBFT_EINVAL, "more than 65536 segments");
+  if (max_stream_bytes > pbft::IX_MAX_STREAM) return set_err(PBFT_EINVAL, "more than 2^31 stream bytes to index");
+  HIP_TRY(hipSetDevice(c->device));
+  return ensure_index(c, max_stream_bytes, max_segments);
+}
+
+int pbft_verify_streams_tally_device(pbft_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes,
+                                     const uint64_t* d_seg_off, const uint64_t* d_seg_len, const uint16_t* d_seg_peer,
+                                     uint32_t S, uint32_t n_replicas, uint64_t frame_cap, uint64_t* d_off,
+                                     uint32_t* d_len, uint16_t* d_peer, pbft_seg_head* d_seg_heads,
+                                     uint32_t* d_n_frames, uint8_t* d_records, pbft_frame_head* d_heads, uint64_t* dB,
+                                     uint32_t env_cap, uint32_t* d_env_idx, uint8_t* d_envelopes, uint32_t* d_n_env,
+                                     uint64_t* d_signers, uint32_t* d_count, void* stream) {
+  if (!c) return set_err(PBFT_EINVAL, "null context");
+  // every check of every step first: a refused call has written nothing
+  int rc = check_index_args(d_stream, stream_bytes, d_seg_off, d_seg_len, d_seg_peer, S, frame_cap, d_off, d_len,
+                            d_peer, d_seg_heads, d_n_frames);
+  if (rc) return rc;
+  const uint64_t N = frame_cap;
+  rc = check_frames_args(d_stream, d_off, d_len, d_peer, n_replicas, N, d_records, d_heads);
+  if (rc) return rc;
+  if (N && !dB) return set_err(PBFT_EINVAL, "null bitmap");
+  if ((uintptr_t)dB & 7) return set_err(PBFT_EINVAL, "misaligned frames pointer");
+  rc = check_group_args(d_records, PBFT_RECORD_BYTES, d_records, PBFT_RECORD_BYTES, N, env_cap, d_env_idx,
+                        d_envelopes, d_n_env);
+  if (rc) return rc;
+  if (env_cap && (!d_signers || !d_count)) return set_err(PBFT_EINVAL, "null tally output");
+  if (((uintptr_t)d_signers & 7) || ((uintptr_t)d_count & 3)) return set_err(PBFT_EINVAL, "misaligned tally pointer");
+  if (c->n_keys == 0) return set_err(PBFT_ENOKEYS, "pbft_verify_set_keys not called");
+  rc = pbft_wire_index_streams_device(c, d_stream, stream_bytes, d_seg_off, d_seg_len, d_seg_peer, S, frame_cap, d_off,
+                                      d_len, d_peer, d_seg_heads, d_n_frames, stream);
+  if (rc) return rc;
+  return pbft_verify_frames_tally_device(c, d_stream, stream_bytes, d_off, d_len, d_peer, n_replicas, N, d_records,
+                                         d_heads, dB, env_cap, d_env_idx, d_envelopes, d_n_env, d_signers, d_count,
+                                         stream);
+}
+
+int pbft_verify_streams_tally(pbft_ctx* c, const uint8_t* stream, uint64_t stream_bytes, const uint64_t* seg_off,
+                              const uint64_t* seg_len, const uint16_t* seg_peer, uint32_t S, uint32_t n_replicas,
+                              uint64_t frame_cap, uint32_t env_cap, uint64_t* out, pbft_frame_head* heads_out,
+                              uint32_t* env_idx_out, uint8_t* envelopes_out, uint32_t* n_env_out,
+                              uint64_t* signers_out, uint32_t* count_out, pbft_seg_head* seg_heads_out,
+                              uint32_t* n_frames_out, uint64_t* off_out, uint32_t* flen_out) {
+  if (!c) return set_err(PBFT_EINVAL, "null context");
+  if (c->in_flight) return set_err(PBFT_EBUSY, "async batch in flight");
+  if (n_replicas == 0 || n_replicas > 65535) return set_err(PBFT_EINVAL, "n_replicas out of range");
+  if (S > pbft::IX_MAX_SEGMENTS) return set_err(PBFT_EINVAL, "more than 65536 segments");
+  if (frame_cap > ((uint64_t)1 << 31)) return set_err(PBFT_EINVAL, "frame_cap above 2^31");
+  if (stream_bytes > pbft::IX_MAX_STREAM) return set_err(PBFT_EINVAL, "more than 2^31 stream bytes to index");
+  if (!n_frames_out || (stream_bytes && !stream) || (S && (!seg_off || !seg_len || !seg_heads_out)) ||
+      (frame_cap && (!out || !heads_out)))
+    return set_err(PBFT_EINVAL, "null streams argument");
+  if (((uintptr_t)seg_off & 7) || ((uintptr_t)seg_len & 7) || ((uintptr_t)seg_peer & 1) || ((uintptr_t)out & 7) ||
+      ((uintptr_t)heads_out & 7) || ((uintptr_t)seg_heads_out & 7) || ((uintptr_t)n_frames_out & 3) ||
+      ((uintptr_t)off_out & 7) || ((uintptr_t)flen_out & 3))
+    return set_err(PBFT_EINVAL, "misaligned streams pointer");
+  if (frame_cap && env_cap == 0) return set_err(PBFT_EINVAL, "env_cap is 0");
+  if (!n_env_out || (env_cap && (!envelopes_out || !signers_out || !count_out)))
+    return set_err(PBFT_EINVAL, "null tally output");
+  if (c->n_keys == 0) return set_err(PBFT_ENOKEYS, "pbft_verify_set_keys not called");
+  HIP_TRY(hipSetDevice(c->device));
+  const uint32_t W = tally_words(c->n_keys);
+  const size_t env_bytes = (size_t)env_cap * PBFT_ENVELOPE_LEN, set_bytes = (size_t)env_cap * W * 8,
+               cnt_bytes = (size_t)env_cap * 4;
+  // the frames staging for frame_cap frames; behind it the segment table, the segment heads and the totals, then
+  // env_idx | envelopes (+16) | n_env | signer sets | counts as in pbft_verify_frames_tally
+  const frames_layout lay(frame_cap, stream_bytes);
+  const size_t o_soff = (lay.total + 15) & ~(size_t)15, o_slen = o_soff + 8 * (size_t)S, o_shead = o_slen + 8 * (size_t)S,
+               o_nfr = o_shead + sizeof(pbft_seg_head) * (size_t)S, o_speer = o_nfr + 8,
+               o_idx = (o_speer + 2 * (size_t)S + 15) & ~(size_t)15,
+               o_env = o_idx + ((4 * (size_t)frame_cap + 15) & ~(size_t)15),
+               o_n = o_env + ((env_bytes + 16 + 15) & ~(size_t)15), o_set = o_n + 16, o_cnt = o_set + set_bytes;
+  int rc = ensure_stage(c, o_cnt + cnt_bytes + 256, (frame_cap + 63) / 64);
+  if (rc) return rc;
+  uint8_t* const d = c->d_stage;
+  pbft_frame_head* const d_heads = (pbft_frame_head*)(d + lay.heads);
+  uint64_t* const d_off = (uint64_t*)(d + lay.off);
+  uint32_t* const d_len = (uint32_t*)(d + lay.len);
+  uint16_t* const d_peer = seg_peer ? (uint16_t*)(d + lay.peer) : nullptr;
+  if (stream_bytes) HIP_TRY(hipMemcpyAsync(d + lay.stream, stream, stream_bytes, hipMemcpyHostToDevice, c->stream));
+  if (S) {
+    HIP_TRY(hipMemcpyAsync(d + o_soff, seg_off, 8 * (size_t)S, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d + o_slen, seg_len, 8 * (size_t)S, hipMemcpyHostToDevice, c->stream));
+    if (seg_peer) HIP_TRY(hipMemcpyAsync(d + o_speer, seg_peer, 2 * (size_t)S, hipMemcpyHostToDevice, c->stream));
+  }
+  rc = pbft_wire_index_streams_device(c, d + lay.stream, stream_bytes, (const uint64_t*)(d + o_soff),
+                                      (const uint64_t*)(d + o_slen), seg_peer ? (const uint16_t*)(d + o_speer) : nullptr,
+                                      S, frame_cap, d_off, d_len, frame_cap ? d_peer : nullptr,
+                                      (pbft_seg_head*)(d + o_shead), (uint32_t*)(d + o_nfr), c->stream);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(n_frames_out, d + o_nfr, 8, hipMemcpyDeviceToHost, c->stream));
+  if (S) HIP_TRY(hipMemcpyAsync(seg_heads_out, d + o_shead, sizeof(pbft_seg_head) * (size_t)S, hipMemcpyDeviceToHost,
+                                c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  const uint64_t N = n_frames_out[0] < frame_cap ? n_frames_out[0] : frame_cap;
+  if (N == 0) {  // no frame: no envelope, empty sets
+    n_env_out[0] = n_env_out[1] = 0;
+    if (env_cap) {
+      memset(envelopes_out, 0, env_bytes);
+      memset(signers_out, 0, set_bytes);
+      memset(count_out, 0, cnt_bytes);
+    }
+    return PBFT_OK;
+  }
+  rc = pbft_wire_decode_frames_device(c, d + lay.stream, stream_bytes, d_off, d_len, d_peer, n_replicas, N, d,
+                                      d_heads, c->stream);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(heads_out, d_heads, sizeof(pbft_frame_head) * N, hipMemcpyDeviceToHost, c->stream));
+  if (off_out) HIP_TRY(hipMemcpyAsync(off_out, d_off, 8 * N, hipMemcpyDeviceToHost, c->stream));
+  if (flen_out) HIP_TRY(hipMemcpyAsync(flen_out, d_len, 4 * N, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  bool deferred = false;
+  for (uint64_t f = 0; f < N && !deferred; ++f) deferred = heads_out[f].status == PBFT_WIRE_EDEFER;
+  if (deferred) {  // the index comes back only now, and only for the host parser's sake
+    std::vector<uint64_t> h_off;
+    std::vector<uint32_t> h_len;
+    std::vector<uint16_t> h_peer;
+    const uint64_t* off = off_out;
+    const uint32_t* flen = flen_out;
+    if (!off) {
+      h_off.resize(N);
+      HIP_TRY(hipMemcpy(h_off.data(), d_off, 8 * N, hipMemcpyDeviceToHost));
+      off = h_off.data();
+    }
+    if (!flen) {
+      h_len.resize(N);
+      HIP_TRY(hipMemcpy(h_len.data(), d_len, 4 * N, hipMemcpyDeviceToHost));
+      flen = h_len.data();
+    }
+    if (seg_peer) {  // frame f's peer is its segment's: the heads say which frames a segment has
+      h_peer.assign(N, 0xFFFF);
+      for (uint32_t s = 0; s < S; ++s) {
+        const uint64_t lo = seg_heads_out[s].first, hi = lo + seg_heads_out[s].n_frames;
+        for (uint64_t f = lo; f < hi && f < N; ++f) h_peer[f] = seg_peer[s];
+      }
+    }
+    rc = frames_settle(c, stream, off, flen, seg_peer ? h_peer.data() : nullptr, n_replicas, N, heads_out, d, d_heads);
+    if (rc) return rc;
+  }
+  uint32_t* const d_idx = (uint32_t*)(d + o_idx);
+  const uint16_t* const d_key = (const uint16_t*)(d + 150);
+  rc = pbft_group_envelopes_device(c, d + 64, PBFT_RECORD_BYTES, d_key, PBFT_RECORD_BYTES, N, env_cap, d_idx,
+                                   d + o_env, (uint32_t*)(d + o_n), c->stream);
+  if (rc) return rc;
+  rc = pbft_verify_records_device(c, d, N, c->d_bitmap, c->stream);
+  if (rc) return rc;
+  rc = pbft_tally_device(c, c->d_bitmap, d_key, PBFT_RECORD_BYTES, d_idx, 4, N, env_cap, c->n_keys, 0,
+                         (uint64_t*)(d + o_set), (uint32_t*)(d + o_cnt), c->stream);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(out, c->d_bitmap, (N + 63) / 64 * 8, hipMemcpyDeviceToHost, c->stream));
+  if (env_idx_out) HIP_TRY(hipMemcpyAsync(env_idx_out, d_idx, 4 * N, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(envelopes_out, d + o_env, env_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(n_env_out, d + o_n, 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(signers_out, d + o_set, set_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(count_out, d + o_cnt, cnt_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return PBFT_OK;
+}
+
 static int run_digest(pbft_ctx* c, int kind, const uint8_t* data, const uint64_t* offsets, const uint32_t* lens,
                       uint64_t N, uint8_t* out) {
   if (!c || (N && (!offsets || !lens || !out))) return set_err(PBFT_EINVAL, "null argument");
@@ -2473,6 +2699,12 @@ int pbft_verify_set_option(pbft_ctx* c, int option, uint64_t value) {
     case PBFT_OPT_GROUP_HASH_BITS:
       if (value > 64) return set_err(PBFT_EINVAL, "group hash bits");
       c->group_hash_bits = (uint32_t)value;
+      return PBFT_OK;
+    case PBFT_OPT_INDEX_TILE:
+      if (value == 0) value = INDEX_TILE_DEFAULT;
+      if (value < pbft::IX_TILE_MIN || value > INDEX_TILE_DEFAULT || (value & (value - 1)))
+        return set_err(PBFT_EINVAL, "index tile bytes");
+      c->index_tile = (uint32_t)value;
       return PBFT_OK;
   }
   return set_err(PBFT_EINVAL, "unknown option");

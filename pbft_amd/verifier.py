@@ -481,6 +481,79 @@ class GpuBatchVerifier:
             _ptr(counts)))
         return out, heads, env_idx, envelopes, n_env, signers, counts
 
+    def index_reserve(self, max_stream_bytes: int, max_segments: int) -> None:
+        """pbft_index_reserve: pre-size the index workspace at the current OPT_INDEX_TILE (required before capturing
+        index_streams_device or verify_streams_tally_device into a graph)."""
+        check(self._lib.pbft_index_reserve(self._ctx, max_stream_bytes, max_segments))
+
+    def index_streams_device(self, d_stream: int, stream_bytes: int, d_seg_off: int, d_seg_len: int, n_segments: int,
+                             frame_cap: int, d_off: int, d_len: int, d_seg_heads: int, d_n_frames: int,
+                             d_seg_peer: int = 0, d_peer: int = 0, stream: int = 0) -> None:
+        """pbft_wire_index_streams_device: enqueue the frame index of n_segments connection segments of one stream (raw
+        device pointers): d_off / d_len / d_peer [frame_cap], d_seg_heads [n_segments] (wire.SegHead), d_n_frames [2]
+        u32 = (total, not written)."""
+        check(self._lib.pbft_wire_index_streams_device(
+            self._ctx, d_stream or None, stream_bytes, d_seg_off or None, d_seg_len or None, d_seg_peer or None,
+            n_segments, frame_cap, d_off or None, d_len or None, d_peer or None, d_seg_heads or None,
+            d_n_frames or None, stream or None))
+
+    def verify_streams_tally_device(self, d_stream: int, stream_bytes: int, d_seg_off: int, d_seg_len: int,
+                                    n_segments: int, n_replicas: int, frame_cap: int, d_off: int, d_len: int,
+                                    d_seg_heads: int, d_n_frames: int, d_records: int, d_heads: int, d_bitmap: int,
+                                    env_cap: int, d_env_idx: int, d_envelopes: int, d_n_env: int, d_signers: int,
+                                    d_count: int, d_seg_peer: int = 0, d_peer: int = 0, stream: int = 0) -> None:
+        """pbft_verify_streams_tally_device: index_streams_device, then verify_frames_tally_device with n = frame_cap
+        on the same stream (reserve(frame_cap), group_reserve(frame_cap) and index_reserve before a capture)."""
+        check(self._lib.pbft_verify_streams_tally_device(
+            self._ctx, d_stream or None, stream_bytes, d_seg_off or None, d_seg_len or None, d_seg_peer or None,
+            n_segments, n_replicas, frame_cap, d_off or None, d_len or None, d_peer or None, d_seg_heads or None,
+            d_n_frames or None, d_records or None, d_heads or None, d_bitmap or None, env_cap, d_env_idx or None,
+            d_envelopes or None, d_n_env or None, d_signers or None, d_count or None, stream or None))
+
+    def verify_streams_tally(self, stream, seg_off, seg_len, frame_cap: int, env_cap: int, seg_peer=None,
+                             n_replicas: int | None = None, want_index: bool = False):
+        """pbft_verify_streams_tally: verify_frames_tally of per-connection segments of `stream`, the frame index made
+        on the GPU.  seg_peer: None or the authenticated replica index of each segment's connection.  Returns a dict:
+        n (frames verified = min(total, frame_cap)), bitmap, heads, env_idx, envelopes, n_env, signers, counts (as
+        verify_frames_tally, the per-frame ones cut to n), seg_heads (wire.SegHead per segment), n_frames (total, not
+        written) and, with want_index, off / flen."""
+        from .wire import FrameHead, SegHead
+        buf = np.ascontiguousarray(np.frombuffer(stream, np.uint8) if isinstance(stream, (bytes, bytearray))
+                                   else stream, np.uint8).reshape(-1)
+        seg_off = np.ascontiguousarray(seg_off, np.uint64).reshape(-1)
+        seg_len = np.ascontiguousarray(seg_len, np.uint64).reshape(-1)
+        s = len(seg_off)
+        if len(seg_len) != s:
+            raise ValueError("seg_off and seg_len must have the same length")
+        if seg_peer is not None:
+            seg_peer = np.ascontiguousarray(seg_peer, np.uint16).reshape(-1)
+            if len(seg_peer) != s:
+                raise ValueError("seg_peer must have one entry per segment")
+        out = np.zeros((frame_cap + 63) // 64, dtype=np.uint64)
+        heads = np.zeros(frame_cap, dtype=FrameHead)
+        env_idx = np.zeros(frame_cap, dtype=np.uint32)
+        envelopes = np.zeros((env_cap, 85), dtype=np.uint8)
+        n_env = np.zeros(2, dtype=np.uint32)
+        signers = np.zeros((env_cap, (self.n_keys + 63) // 64), dtype=np.uint64)
+        counts = np.zeros(env_cap, dtype=np.uint32)
+        seg_heads = np.zeros(s, dtype=SegHead)
+        n_frames = np.zeros(2, dtype=np.uint32)
+        off = np.zeros(frame_cap, dtype=np.uint64) if want_index else None
+        flen = np.zeros(frame_cap, dtype=np.uint32) if want_index else None
+        check(self._lib.pbft_verify_streams_tally(
+            self._ctx, _ptr(buf), len(buf), _ptr(seg_off), _ptr(seg_len),
+            _ptr(seg_peer) if seg_peer is not None else None, s,
+            self.n_keys if n_replicas is None else n_replicas, frame_cap, env_cap, _ptr(out), _ptr(heads),
+            _ptr(env_idx), _ptr(envelopes), n_env.ctypes.data, _ptr(signers), _ptr(counts), _ptr(seg_heads),
+            n_frames.ctypes.data, _ptr(off) if want_index else None, _ptr(flen) if want_index else None))
+        n = min(int(n_frames[0]), frame_cap)
+        res = dict(n=n, bitmap=out[:(n + 63) // 64], heads=heads[:n], env_idx=env_idx[:n], envelopes=envelopes,
+                   n_env=n_env, signers=signers, counts=counts, seg_heads=seg_heads, n_frames=n_frames)
+        if want_index:
+            res.update(off=off[:n], flen=flen[:n])
+        return res
+
+    OPT_INDEX_TILE = 19
     OPT_GROUP_SEED, OPT_GROUP_HASH_BITS = 16, 17
     OPT_SPLIT_BELOW, OPT_FINISH_WIDTH, OPT_KEY_TABLE_BUDGET_MB, OPT_FINISH_TREE, OPT_LAT_SPLIT = 1, 2, 3, 4, 5
     OPT_KERNEL_TIMING = 7

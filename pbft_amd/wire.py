@@ -24,6 +24,10 @@ FRAME_MIN, FRAME_MAX = 336, 379  # byte lengths of a canonical signed vote
 FrameHead = np.dtype([("view", "<u8"), ("seq", "<u8"), ("key_idx", "<u2"), ("kind", "u1"), ("status", "u1"),
                       ("frame_len", "<u4")])
 assert FrameHead.itemsize == 24
+# pbft_seg_head (include/pbft_wire.h): one per segment of index_streams_device / verify_streams_tally
+SegHead = np.dtype([("consumed", "<u8"), ("first", "<u4"), ("n_frames", "<u4"), ("status", "<u4"), ("pad", "<u4")])
+assert SegHead.itemsize == 24
+SEG_OK, SEG_EFRAMING, SEG_EOUTSIDE = 0, 1, 2  # PBFT_SEG_*
 
 
 class _Msg(ctypes.Structure):
