@@ -79,6 +79,7 @@
 #include <stdint.h>
 
 #include "pbft_verify.h"
+#include "pbft_wire.h" /* pbft_seg_head (pbft_replica_push_streams) */
 
 #ifdef __cplusplus
 extern "C" {
@@ -256,6 +257,59 @@ int pbft_replica_push_frames(pbft_replica *r, uint32_t peer_idx, const uint8_t *
  * first negative code of a push (then *consumed stops before that record). */
 int pbft_replica_push_records(pbft_replica *r, uint32_t peer_idx, const uint8_t *stream, size_t len,
                               uint64_t *consumed, uint64_t *pushed, uint64_t *dropped);
+
+/* Ingress from every connection at once: bytes in, events out.  stream holds S segments, one authenticated
+ * connection's bytes each (segment s = [seg_off[s], seg_off[s] + seg_len[s]), from a frame boundary on, ending wherever
+ * the socket stopped; seg_peer[s] = its peer), as pbft_verify_streams_tally takes them (include/pbft_wire.h).  The call
+ * is equivalent to
+ *     pbft_replica_flush(r, 1, ...);
+ *     pbft_replica_push_frames(r, seg_peer[s], stream + seg_off[s], seg_len[s], ...)   for s = 0 .. S - 1, in order;
+ *     pbft_replica_flush(r, 1, ...);
+ * with seg_heads_out[s] = {consumed, first, n_frames, status} of segment s (PBFT_SEG_EFRAMING where push_frames
+ * returns PBFT_EINVAL: the frames in front of the error are ingested, the other segments are unaffected), *pushed and
+ * *dropped the sums, and the events of both flushes delivered sorted by (view, seq, kind) (those beyond max_events
+ * stay queued).  Equivalent means: the same consumed per segment, the same prepared / committed_local answers, the
+ * same events, the same accepted, rejected_sig, rejected_digest, rejected_view, rejected_watermark, rejected_signer,
+ * duplicates, dropped_flood, windows_gc, low_watermark and live_windows, the same *pushed and *dropped.  The stats
+ * fields pushed, verified, batches and every _ns field may differ.
+ * How: the frame index, the decode, the admission pass (pbft_admit_device), the grouping, the verification and two
+ * tallies run on the replica's GPU context; per envelope two signer sets come back (who sent it, whose signature
+ * verified) and are applied to the windows in one step; only the residue -- contested votes, PrePrepares, frames the
+ * device decoder deferred -- goes frame by frame through the code pbft_replica_push_frames runs.  With a verifier
+ * override (pbft_replica_set_verifier) the same front half runs on the host.  The whole call falls back to the host
+ * sequence above (exact, slow, counted in the streams stats) when the frames exceed frame_cap, the distinct envelopes
+ * env_cap or the residue residue_cap of pbft_replica_reserve_streams, when 2 * log_window * n > 2^30, for a replica of
+ * several contexts (pbft_replica_create_multi), under a votes-form override (pbft_replica_set_votes_verifier), and when
+ * a frame of the residue turns out to be a vote (in a form the device decoder defers) whose (kind, seq, signer) a clean
+ * row of the call has too: the two would meet in one phase, so the clean row is not independent of the residue.
+ * PBFT_EINVAL: a null argument, seg_peer[s] >= n, a segment that does not lie inside stream_bytes, segments that add
+ * up to more than stream_bytes, S > 65536, stream_bytes > 2^31.  PBFT_EBUSY while a batch is in flight. */
+typedef struct {
+  uint64_t calls_device;       /* calls whose front half ran on the GPU context                          */
+  uint64_t calls_host_front;   /* calls whose front half ran on the host (verifier override installed)   */
+  uint64_t fallback_frames;    /* whole-call fallbacks: frames > frame_cap                               */
+  uint64_t fallback_envelopes; /*   distinct envelopes > env_cap                                         */
+  uint64_t fallback_residue;   /*   residue > residue_cap                                                */
+  uint64_t fallback_planes;    /*   2 * log_window * n > 2^30                                            */
+  uint64_t fallback_multi;     /*   a replica of several contexts                                        */
+  uint64_t fallback_verifier;  /*   a votes-form verifier override                                       */
+  uint64_t fallback_deferred;  /*   a vote in a deferred (non-canonical) form shares its (kind, seq, signer)
+                                    with a clean row of the call                                         */
+  uint64_t clean_rows;         /* votes applied as signer sets (front-half calls only)                   */
+  uint64_t residue_rows;       /* frames that went through the per-frame host code                       */
+  uint64_t envelopes;          /* distinct envelopes of the clean rows                                   */
+  uint64_t front_ns;           /* host time inside the front half (GPU chain or host loops), summed       */
+  uint64_t apply_sets_ns;      /* host time applying the signer sets to the windows, summed              */
+} pbft_replica_streams_stats;
+int pbft_replica_push_streams(pbft_replica *r, const uint8_t *stream, uint64_t stream_bytes, const uint64_t *seg_off,
+                              const uint64_t *seg_len, const uint16_t *seg_peer, uint32_t S,
+                              pbft_seg_head *seg_heads_out, uint64_t *pushed, uint64_t *dropped,
+                              pbft_round_event *events, uint32_t max_events, uint32_t *n_events);
+/* Caps of the next pbft_replica_push_streams calls (defaults: frame_cap 2^16, env_cap 2^12, residue_cap 2^12) and,
+ * with a GPU context, its buffers and workspaces sized for them, so that a call within the caps allocates nothing. */
+int pbft_replica_reserve_streams(pbft_replica *r, uint64_t max_stream_bytes, uint32_t max_segments, uint64_t frame_cap,
+                                 uint32_t env_cap, uint32_t residue_cap);
+int pbft_replica_get_streams_stats(pbft_replica *r, pbft_replica_streams_stats *out);
 
 /* Non-blocking flush.  _submit: collect every READY sub-window (force = every pending candidate) into one
  * batch and launch it; *n_rows = its signatures (0: nothing launched); PBFT_EBUSY while a batch is in flight.

@@ -283,6 +283,70 @@ int pbft_verify_streams_tally(pbft_ctx *ctx, const uint8_t *stream, uint64_t str
                               uint64_t *signers_out, uint32_t *count_out, pbft_seg_head *seg_heads_out,
                               uint32_t *n_frames_out, uint64_t *off_out, uint32_t *flen_out);
 
+/* ---- The replica's admission pass on the device (kernels: pbft_amd/csrc/admit.hip; rule: admit_core.h) ----
+ * What pbft_replica_push_frames does with a frame before it touches a round window, for N decoded frames at once,
+ * from their heads and the replica's (view, h, log_window).  The view is tested before the window, as
+ * pbft_replica_push does; the window is seq in (h, h + log_window] (seq - h <= log_window: a window that reaches past
+ * 2^64 - 1 ends there).  Frame f gets one class: */
+#define PBFT_ADMIT_CLEAN 0         /* an OK Prepare / Commit of this view inside the window, the only such row of its
+                                      (kind, seq, signer) in the call: what becomes of it is a function of the
+                                      window's state and of two signer sets per envelope */
+#define PBFT_ADMIT_CONTESTED 1     /* ... that shares its (kind, seq, signer) with another such row (found exactly) */
+#define PBFT_ADMIT_REJ_VIEW 2      /* an OK vote of another view */
+#define PBFT_ADMIT_REJ_WATERMARK 3 /* an OK vote of this view outside the window */
+#define PBFT_ADMIT_REJ_SIGNER 4    /* PBFT_WIRE_ESIGNER (also an OK vote whose key index is >= n_keys) */
+#define PBFT_ADMIT_HOST 5          /* every other status that is not PBFT_WIRE_OK (PBFT_WIRE_EDEFER: a PrePrepare, a
+                                      ClientRequest, a non-canonical vote), and an OK head of kind 0 */
+#define PBFT_ADMIT_PAD 6           /* f >= min(d_n_frames[0], N): the index's padding */
+#define PBFT_ADMIT_CLASSES 8       /* entries of d_counts (entry 7 is 0) */
+typedef struct {
+  uint64_t off;   /* d_off[frame]: the body's absolute offset in the stream */
+  uint32_t frame; /* the frame's number */
+  uint32_t len;   /* d_len[frame] */
+} pbft_admit_residue;
+
+/* Device, enqueue only (five kernel nodes on one stream: no allocation, copy, memset or synchronisation, no lane waits
+ * for another block; capturable after pbft_admit_reserve).  d_heads [N] and d_records [N][160] as the frame decoder
+ * wrote them; d_off / d_len [N]: the index (NULL: the residue's off / len are 0); d_n_frames: NULL (all N rows are
+ * frames) or the index's {total, not written}, read on the device.  Outputs: d_class [N] bytes; d_counts
+ * [PBFT_ADMIT_CLASSES] rows per class; d_clean [ceil(N / 64)] bit f = frame f is clean; d_res [residue_cap] the frames
+ * of class CONTESTED or HOST in frame order (entries from min(total, residue_cap) on are zero) and d_n_res [2] =
+ * {total, not written}; and, in place, key index 0xFFFF at byte 150 of the record of every row that is not clean, so
+ * that pbft_group_envelopes_device, pbft_verify_records_device and pbft_tally_device skip it without change.
+ * PBFT_EINVAL: a null pointer that would be used or a misaligned one, N > 2^31, n_keys 0 or > 65535, log_window 0 or
+ * 2 * log_window * n_keys > 2^30 (the two key planes have one bit per (kind, seq, signer) of the window); a refused
+ * call has enqueued nothing.  The workspace (2 * log_window * n_keys / 4 bytes, plus 1.5 bits per row) grows on first
+ * use of a larger call, which is then not capturable. */
+int pbft_admit_device(pbft_ctx *ctx, const pbft_frame_head *d_heads, uint8_t *d_records, const uint64_t *d_off,
+                      const uint32_t *d_len, const uint32_t *d_n_frames, uint64_t N, uint64_t view, uint64_t h,
+                      uint64_t log_window, uint32_t n_keys, uint32_t residue_cap, uint8_t *d_class, uint32_t *d_counts,
+                      uint64_t *d_clean, pbft_admit_residue *d_res, uint32_t *d_n_res, void *stream);
+
+/* Pre-size the admission workspace for calls of up to max_n rows at (log_window, n_keys): required before a capture. */
+int pbft_admit_reserve(pbft_ctx *ctx, uint64_t log_window, uint32_t n_keys, uint64_t max_n);
+
+/* Host, blocking: connection streams in, signer sets out -- the device half of pbft_replica_push_streams
+ * (include/pbft_replica.h).  The stream and the segment table go up; then, enqueued once over N = frame_cap rows on
+ * the context's stream: pbft_wire_index_streams_device, pbft_wire_decode_frames_device (peer = the segment's,
+ * n_replicas), pbft_admit_device (n_keys = n_replicas), pbft_group_envelopes_device, pbft_verify_records_device,
+ * pbft_tally_device over the clean bitmap (present_out: who sent each envelope) and pbft_tally_device over the verify
+ * bitmap (valid_out: whose signature verified); rows that are not clean carry key index 0xFFFF and take part in
+ * neither.  Back: seg_heads_out [S], n_frames_out [2], counts_out [PBFT_ADMIT_CLASSES], envelopes_out [env_cap][85],
+ * n_env_out [2], present_out / valid_out [env_cap][ceil(n_replicas / 64)], res_out [residue_cap], n_res_out [2];
+ * nothing per clean vote.  The caller compares n_frames_out[0] with frame_cap, n_env_out[0] with env_cap and
+ * n_res_out[0] with residue_cap: beyond a cap the outputs are incomplete (never wrong for what they hold).
+ * PBFT_EINVAL: a null argument, frame_cap or env_cap 0, and the range checks of the functions above; PBFT_ENOKEYS with
+ * fewer than n_replicas keys installed; PBFT_EBUSY while an asynchronous batch is in flight. */
+int pbft_verify_streams_admit(pbft_ctx *ctx, const uint8_t *stream, uint64_t stream_bytes, const uint64_t *seg_off,
+                              const uint64_t *seg_len, const uint16_t *seg_peer, uint32_t S, uint32_t n_replicas,
+                              uint64_t frame_cap, uint32_t env_cap, uint32_t residue_cap, uint64_t view, uint64_t h,
+                              uint64_t log_window, pbft_seg_head *seg_heads_out, uint32_t *n_frames_out,
+                              uint32_t *counts_out, uint8_t *envelopes_out, uint32_t *n_env_out, uint64_t *present_out,
+                              uint64_t *valid_out, pbft_admit_residue *res_out, uint32_t *n_res_out);
+/* Size the staging and the index, grouping, admission and verification workspaces of the call above for these caps. */
+int pbft_streams_admit_reserve(pbft_ctx *ctx, uint64_t max_stream_bytes, uint32_t max_segments, uint32_t n_replicas,
+                               uint64_t frame_cap, uint32_t env_cap, uint32_t residue_cap, uint64_t log_window);
+
 #ifdef __cplusplus
 }
 #endif

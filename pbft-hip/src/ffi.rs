@@ -59,6 +59,23 @@ pub const PBFT_SEG_OK: u32 = 0;
 pub const PBFT_SEG_EFRAMING: u32 = 1;
 pub const PBFT_SEG_EOUTSIDE: u32 = 2;
 
+/// One residue entry of pbft_admit_device: 16 bytes.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct pbft_admit_residue {
+    pub off: u64,
+    pub frame: u32,
+    pub len: u32,
+}
+pub const PBFT_ADMIT_CLEAN: u8 = 0;
+pub const PBFT_ADMIT_CONTESTED: u8 = 1;
+pub const PBFT_ADMIT_REJ_VIEW: u8 = 2;
+pub const PBFT_ADMIT_REJ_WATERMARK: u8 = 3;
+pub const PBFT_ADMIT_REJ_SIGNER: u8 = 4;
+pub const PBFT_ADMIT_HOST: u8 = 5;
+pub const PBFT_ADMIT_PAD: u8 = 6;
+pub const PBFT_ADMIT_CLASSES: usize = 8;
+
 pub const PBFT_WIRE_OK: u8 = 0;
 pub const PBFT_WIRE_EDEFER: u8 = 6;
 pub const PBFT_FRAME_MIN: u32 = 336;
@@ -127,6 +144,26 @@ pub struct pbft_replica_stats {
     pub live_windows: u64,
     pub submit_ns: u64,
     pub apply_ns: u64,
+}
+
+/// Counters of pbft_replica_push_streams (pbft_replica_get_streams_stats).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct pbft_replica_streams_stats {
+    pub calls_device: u64,
+    pub calls_host_front: u64,
+    pub fallback_frames: u64,
+    pub fallback_envelopes: u64,
+    pub fallback_residue: u64,
+    pub fallback_planes: u64,
+    pub fallback_multi: u64,
+    pub fallback_verifier: u64,
+    pub fallback_deferred: u64,
+    pub clean_rows: u64,
+    pub residue_rows: u64,
+    pub envelopes: u64,
+    pub front_ns: u64,
+    pub apply_sets_ns: u64,
 }
 
 /// Phases of the last push_many / flush (pbft_replica_get_timings; host clock, ns).
@@ -394,4 +431,26 @@ extern "C" {
                                      n_env_out: *mut u32, signers_out: *mut u64, count_out: *mut u32,
                                      seg_heads_out: *mut pbft_seg_head, n_frames_out: *mut u32, off_out: *mut u64,
                                      flen_out: *mut u32) -> c_int;
+    pub fn pbft_admit_device(ctx: *mut pbft_ctx, d_heads: *const pbft_frame_head, d_records: *mut u8,
+                             d_off: *const u64, d_len: *const u32, d_n_frames: *const u32, n: u64, view: u64, h: u64,
+                             log_window: u64, n_keys: u32, residue_cap: u32, d_class: *mut u8, d_counts: *mut u32,
+                             d_clean: *mut u64, d_res: *mut pbft_admit_residue, d_n_res: *mut u32,
+                             stream: *mut c_void) -> c_int;
+    pub fn pbft_admit_reserve(ctx: *mut pbft_ctx, log_window: u64, n_keys: u32, max_n: u64) -> c_int;
+    pub fn pbft_verify_streams_admit(ctx: *mut pbft_ctx, stream: *const u8, stream_bytes: u64, seg_off: *const u64,
+                                     seg_len: *const u64, seg_peer: *const u16, n_segments: u32, n_replicas: u32,
+                                     frame_cap: u64, env_cap: u32, residue_cap: u32, view: u64, h: u64,
+                                     log_window: u64, seg_heads_out: *mut pbft_seg_head, n_frames_out: *mut u32,
+                                     counts_out: *mut u32, envelopes_out: *mut u8, n_env_out: *mut u32,
+                                     present_out: *mut u64, valid_out: *mut u64, res_out: *mut pbft_admit_residue,
+                                     n_res_out: *mut u32) -> c_int;
+    pub fn pbft_streams_admit_reserve(ctx: *mut pbft_ctx, max_stream_bytes: u64, max_segments: u32, n_replicas: u32,
+                                      frame_cap: u64, env_cap: u32, residue_cap: u32, log_window: u64) -> c_int;
+    pub fn pbft_replica_push_streams(r: *mut pbft_replica, stream: *const u8, stream_bytes: u64, seg_off: *const u64,
+                                     seg_len: *const u64, seg_peer: *const u16, n_segments: u32,
+                                     seg_heads_out: *mut pbft_seg_head, pushed: *mut u64, dropped: *mut u64,
+                                     events: *mut pbft_round_event, max_events: u32, n_events: *mut u32) -> c_int;
+    pub fn pbft_replica_reserve_streams(r: *mut pbft_replica, max_stream_bytes: u64, max_segments: u32,
+                                        frame_cap: u64, env_cap: u32, residue_cap: u32) -> c_int;
+    pub fn pbft_replica_get_streams_stats(r: *mut pbft_replica, out: *mut pbft_replica_streams_stats) -> c_int;
 }

@@ -793,6 +793,39 @@ impl<'a> Replica<'a> {
         })?;
         Ok(used as usize)
     }
+    /// Every connection's bytes at once (pbft_replica_push_streams): `segments[i]` = (offset, length, authenticated
+    /// peer) of one connection's bytes in `stream`, from a frame boundary on.  Equivalent to a forced flush, one
+    /// `push_frames` per segment and another forced flush, with the index, the decode, the admission, the grouping, the
+    /// verification and the tallies on the GPU.  Returns the per-segment heads (`consumed`: keep the rest for the next
+    /// read), the votes pushed, the frames dropped and the round events sorted by (view, seq, kind).
+    pub fn push_streams(&mut self, stream: &[u8], segments: &[(u64, u64, u16)], max_events: usize)
+                        -> Result<(Vec<ffi::pbft_seg_head>, u64, u64, Vec<ffi::pbft_round_event>)> {
+        let off: Vec<u64> = segments.iter().map(|s| s.0).collect();
+        let len: Vec<u64> = segments.iter().map(|s| s.1).collect();
+        let peer: Vec<u16> = segments.iter().map(|s| s.2).collect();
+        let mut heads = vec![ffi::pbft_seg_head::default(); segments.len()];
+        let mut events = vec![ffi::pbft_round_event::default(); max_events];
+        let (mut pushed, mut dropped, mut n_events) = (0u64, 0u64, 0u32);
+        check(unsafe {
+            ffi::pbft_replica_push_streams(self.raw, stream.as_ptr(), stream.len() as u64, off.as_ptr(), len.as_ptr(),
+                                           peer.as_ptr(), segments.len() as u32, heads.as_mut_ptr(), &mut pushed,
+                                           &mut dropped, events.as_mut_ptr(), max_events as u32, &mut n_events)
+        })?;
+        events.truncate(n_events as usize);
+        Ok((heads, pushed, dropped, events))
+    }
+    /// Caps and buffers of the next `push_streams` calls (pbft_replica_reserve_streams).
+    pub fn reserve_streams(&mut self, max_stream_bytes: u64, max_segments: u32, frame_cap: u64, env_cap: u32,
+                           residue_cap: u32) -> Result<()> {
+        check(unsafe {
+            ffi::pbft_replica_reserve_streams(self.raw, max_stream_bytes, max_segments, frame_cap, env_cap, residue_cap)
+        }).map(|_| ())
+    }
+    pub fn streams_stats(&self) -> ffi::pbft_replica_streams_stats {
+        let mut s = ffi::pbft_replica_streams_stats::default();
+        unsafe { ffi::pbft_replica_get_streams_stats(self.raw, &mut s) };
+        s
+    }
     /// 160-byte binary records (pbft_wire.h PBFT_RECORD_BYTES) read from peer `peer_idx`'s connection;
     /// returns (bytes consumed, votes pushed, records dropped) -- keep the unconsumed tail for the next read.
     pub fn push_records(&mut self, peer_idx: u32, stream: &[u8]) -> Result<(usize, u64, u64)> {

@@ -6,8 +6,9 @@ tests and bench.py; it never computes a signature check itself.
 """
 from ._lib import EXPORTS, LIB_PATH, PbftError, load  # noqa: F401
 from .verifier import (ENV_NONE, TALLY_ACCUMULATE, GpuBatchVerifier, MultiGpu, SigBatch,  # noqa: F401
-                       bitmap_to_bool, group_reference, quorum, tally_reference, verify_multi)
-from .wire import FrameHead, SegHead, frame_index  # noqa: F401
+                       admit_reference, bitmap_to_bool, group_reference, quorum, tally_reference, verify_multi)
+from .wire import AdmitResidue, FrameHead, SegHead, frame_index  # noqa: F401
 
 __all__ = ["GpuBatchVerifier", "MultiGpu", "SigBatch", "bitmap_to_bool", "verify_multi", "tally_reference", "quorum",
-           "group_reference", "ENV_NONE", "TALLY_ACCUMULATE", "FrameHead", "SegHead", "frame_index", "PbftError", "load", "LIB_PATH", "EXPORTS"]
+           "group_reference", "ENV_NONE", "TALLY_ACCUMULATE", "FrameHead", "SegHead", "AdmitResidue", "admit_reference", "frame_index", "PbftError", "load", "LIB_PATH",
+           "EXPORTS"]

@@ -29,7 +29,8 @@ EXPORTS = (
     "pbft_verify_records", "pbft_wire_encode_votes", "pbft_wire_frame_index", "pbft_wire_decode_frames_device",
     "pbft_verify_frames_device", "pbft_verify_frames", "pbft_verify_frames_tally_device", "pbft_verify_frames_tally",
     "pbft_wire_index_streams_device", "pbft_index_reserve", "pbft_verify_streams_tally_device",
-    "pbft_verify_streams_tally",
+    "pbft_verify_streams_tally", "pbft_admit_device", "pbft_admit_reserve", "pbft_verify_streams_admit",
+    "pbft_streams_admit_reserve",
 )
 
 ERRORS = {0: "PBFT_OK", -1: "PBFT_EINVAL", -2: "PBFT_EHIP", -3: "PBFT_ENOKEYS",
@@ -135,6 +136,11 @@ def load() -> ctypes.CDLL:
                                                    vp, u32, vp, vp, vp, vp, vp, vp]),
         "pbft_verify_streams_tally": (i32, [vp, vp, u64, vp, vp, vp, u32, u32, u64, u32, vp, vp, vp, vp, vp, vp, vp,
                                             vp, vp, vp, vp]),
+        "pbft_admit_device": (i32, [vp, vp, vp, vp, vp, vp, u64, u64, u64, u64, u32, u32, vp, vp, vp, vp, vp, vp]),
+        "pbft_admit_reserve": (i32, [vp, u64, u32, u64]),
+        "pbft_verify_streams_admit": (i32, [vp, vp, u64, vp, vp, vp, u32, u32, u64, u32, u32, u64, u64, u64, vp, vp, vp,
+                                            vp, vp, vp, vp, vp, vp]),
+        "pbft_streams_admit_reserve": (i32, [vp, u64, u32, u32, u64, u32, u32, u64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -37,12 +37,21 @@
 #if defined(__x86_64__)
 #include <immintrin.h>
 #endif
+#include <tuple>
 #include <unordered_map>
 #include <utility>
 #include <vector>
 
 #include "../../../include/pbft_replica.h"
 #include "../../../include/pbft_wire.h"
+#include "../admit_core.h"
+#include "../wire_decode_core.h"
+
+// The device half of pbft_replica_push_streams lives in the GPU library (pbft_verify.hip).  Weak, so that this file
+// still links on its own into the host-only programs that test the state machine: there the symbols are null and a
+// replica without a verifier override reports PBFT_ENODEV.
+#pragma weak pbft_verify_streams_admit
+#pragma weak pbft_streams_admit_reserve
 
 namespace {
 
@@ -214,6 +223,28 @@ struct Seg {
   uint32_t count;
   uint32_t env0;  // its envelopes: env0 + index into the phase's digs
   uint8_t kind;   // 0 PrePrepare, 1 Prepare, 2 Commit
+};
+
+// pbft_replica_push_streams: the clean votes of one envelope as two signer sets (bit s of word s / 64), queued until
+// the next flush_poll applies them.  `present` holds the signers whose vote was queued (duplicates already counted).
+struct PendingSet {
+  uint8_t kind;  // 1 Prepare, 2 Commit
+  uint64_t seq;  // (of the current view, inside the log when it was queued)
+  Digest digest;
+  std::vector<uint64_t> present, valid;
+};
+
+// What the front half of pbft_replica_push_streams (the GPU chain, or the host loops under a verifier override)
+// hands to the state machine; also the call's caps (pbft_replica_reserve_streams).
+struct StreamsFront {
+  uint64_t frame_cap = 1u << 16;
+  uint32_t env_cap = 1u << 12, residue_cap = 1u << 12;
+  std::vector<pbft_seg_head> seg;
+  uint32_t n_frames[2] = {0, 0}, counts[pbft::ADMIT_CLASSES] = {0}, n_env[2] = {0, 0}, n_res[2] = {0, 0};
+  uint32_t W = 1;  // words per signer set
+  std::vector<uint8_t> envelopes;        // [env_cap][85]
+  std::vector<uint64_t> present, valid;  // [env_cap][W]
+  std::vector<pbft_admit_residue> res;   // [residue_cap]
 };
 
 // Worker threads for the batch fill and the bitmap application: one pool per process, started on first use and
@@ -492,6 +523,11 @@ struct pbft_replica {
   std::vector<uint8_t> hSig, hR, hS, hM, hE;
   std::vector<uint16_t> hK;
   std::vector<uint32_t> hI;
+  // pbft_replica_push_streams
+  std::vector<PendingSet> pend;  // signer sets queued for the next flush_poll
+  bool defer_eval = false;       // the batch in flight shares windows with `pend`: they are evaluated once, after both
+  StreamsFront front;
+  pbft_replica_streams_stats sstats{};
 };
 
 static uint32_t primary_of(const pbft_replica* r, uint64_t view) { return (uint32_t)(view % r->n); }
@@ -732,7 +768,8 @@ static void early_single(pbft_replica* r) {
   r->eu.envs = A.ne;
 }
 
-static bool in_log(const pbft_replica* r, uint64_t seq) { return seq > r->h && seq - r->h <= r->log_window; }
+// (the predicate is admit_core.h's, the one text the device's admission pass builds too)
+static bool in_log(const pbft_replica* r, uint64_t seq) { return pbft::admit_in_log(r->h, r->log_window, seq); }
 
 // accepted votes of phase p matching the window's digest (optionally not counting one signer)
 static uint32_t matching(const Window& w, const Phase& p, int64_t exclude = -1) {
@@ -1100,7 +1137,8 @@ static void apply_range(pbft_replica* r, size_t s0, size_t s1, uint64_t st_out[3
     if (gi + 1 == r->segs.size() || r->segs[gi + 1].key != g.key) {
       bool any = false;
       for (size_t gj = gi + 1; gj-- > 0 && r->segs[gj].key == g.key;) any = any || touched[gj];
-      if (any) evaluate_window(r, g.key.first, g.key.second, w, events);
+      // (not while signer sets wait for the same flush_poll: the window is evaluated once, after both)
+      if (any && !r->defer_eval) evaluate_window(r, g.key.first, g.key.second, w, events);
     }
   }
   release_counts(r, rel);
@@ -1170,6 +1208,7 @@ static void mark_dirty(pbft_replica* r) {
 
 static void finish_batch(pbft_replica* r) {
   apply_segs(r, r->seg_next, r->segs.size());  // (windows evaluated as their last segments are applied)
+  if (r->defer_eval) mark_dirty(r);            // (... or left to flush_poll's evaluate: pending signer sets)
   ++r->stats.batches;
   r->stats.verified += r->rows;
   r->segs.clear();
@@ -2419,6 +2458,47 @@ static int flush_submit_impl(pbft_replica* r, int force, uint64_t* n_rows) {
   return PBFT_OK;
 }
 
+// The signer sets pbft_replica_push_streams queued, applied to their windows: for signer s of `present`, what
+// apply_range does with the one verified candidate a push of s's vote would have left in the phase -- accepted if s is
+// in `valid` (acc, acc_cnt and distinct move as there: the last accepted vote of a signer wins; rejected_digest if the
+// window has another digest), else rejected_sig.  A clean vote is the only row of its (kind, seq, signer) in its call,
+// so the candidate rules (PBFT_MAX_CANDIDATES, flood drop) cannot fire and no other row of the call touches acc[s].
+static void apply_pending_sets(pbft_replica* r) {
+  if (r->pend.empty()) { r->defer_eval = false; return; }
+  const auto t0 = std::chrono::steady_clock::now();
+  for (const PendingSet& ps : r->pend) {
+    Window* wp = find_window(r, r->current_view, ps.seq);
+    if (!wp) continue;  // (erased by a stable checkpoint since)
+    Window& w = *wp;
+    Phase& p = w.ph[ps.kind];
+    p.init(r->n);
+    const bool mism = w.have_pre_prepare && ps.digest != w.digest;
+    uint32_t a = 0, accepted = 0;
+    for (size_t wi = 0; wi < ps.present.size(); ++wi) {
+      for (uint64_t m = ps.present[wi]; m; m &= m - 1) {
+        const uint32_t s = (uint32_t)(64 * wi) + (uint32_t)__builtin_ctzll(m);
+        if (s >= r->n) continue;
+        if (!((ps.valid[wi] >> (s & 63)) & 1)) { ++r->stats.rejected_sig; continue; }
+        ++accepted;
+        if (!a) a = p.acc_index(ps.digest) + 1;
+        const uint32_t prev = p.acc[s];
+        if (prev != a) {
+          if (prev) --p.acc_cnt[prev - 1];
+          else ++p.distinct;  // (a push counts a signer with neither a candidate nor an accepted vote)
+          p.acc[s] = a;
+          ++p.acc_cnt[a - 1];
+        }
+      }
+    }
+    r->stats.accepted += accepted;
+    if (mism) r->stats.rejected_digest += accepted;
+    if (accepted) mark_window_dirty(r, w);
+  }
+  r->pend.clear();
+  r->defer_eval = false;
+  r->sstats.apply_sets_ns += ns_since(t0);
+}
+
 // 1 = no batch in flight any more (the finished one applied; events of every dirty window queued and delivered
 // up to max_events -- the rest wait for the next call); 0 = still running; < 0 = the batch failed (its
 // candidates are pending again).
@@ -2480,6 +2560,7 @@ int pbft_replica_flush_poll(pbft_replica* r, pbft_round_event* events, uint32_t 
     finish_batch(r);
     RTRACE(r, "finish_batch", 0);
     r->tm.apply_final_ns = ns_since(t0);
+    apply_pending_sets(r);  // (after the batch's rows: a PrePrepare of the same call has fixed its window's digest)
     const auto t1 = std::chrono::steady_clock::now();
     evaluate(r);
     RTRACE(r, "evaluate", r->evq.size());
@@ -2495,6 +2576,7 @@ int pbft_replica_flush_poll(pbft_replica* r, pbft_round_event* events, uint32_t 
       r->trace.clear();
     }
   } else {
+    apply_pending_sets(r);
     evaluate(r);
     gc(r);
   }
@@ -2537,10 +2619,33 @@ int pbft_replica_in_flight(pbft_replica* r) { return r ? (r->in_flight ? 1 : 0) 
 
 // One connection's byte stream of UviBytes/JSON frames (src/protocol_config.rs:49-69 ->
 // src/handler.rs:533-548 -> inject_node_event).  peer_idx = the authenticated peer.
+// One whole frame body (JSON) read from peer_idx's connection: 1 queued, 0 dropped, < 0 a push's error.
+static int push_frame_body(pbft_replica* r, uint32_t peer_idx, const char* js, size_t fl) {
+  static thread_local char arena[1 << 16];  // unescaped strings (the PrePrepare's operation)
+  pbft_wire_msg m;
+  const bool parsed = pbft_wire_decode_json(js, fl, &m, arena, sizeof arena) == 0;
+  if (!parsed || !m.digest_ok || !m.has_sig)
+    return 0;  // not a signed PBFT message (the reference would panic in serde_json .unwrap(), src/message.rs:17-18)
+  if (m.kind == PBFT_MSG_PREPARE || m.kind == PBFT_MSG_COMMIT) {
+    // the signer is the authenticated connection (src/behavior.rs:346, :380), never the frame's field
+    if (m.replica != peer_idx) { ++r->stats.rejected_signer; return 0; }
+    return pbft_replica_push(r, (uint8_t)m.kind, m.view, m.seq, m.digest, peer_idx, m.sig);
+  }
+  if (m.kind == PBFT_MSG_PREPREPARE) {
+    // only on the primary's own connection (the reference receives it from the primary, src/behavior.rs:89-95):
+    // a relayed PrePrepare could otherwise fill the window's candidate slots ahead of the real one
+    const uint32_t p = r->n ? primary_of(r, m.view) : 0;
+    if (r->n == 0 || m.replica != p) { ++r->stats.rejected_signer; return 0; }
+    // (on_pre_prepare rejects a connection that is not the primary's)
+    return pbft_replica_on_pre_prepare(r, peer_idx, m.view, m.seq, (const uint8_t*)m.operation, m.operation_len,
+                                       m.digest, m.sig, nullptr);
+  }
+  return 0;
+}
+
 int pbft_replica_push_frames(pbft_replica* r, uint32_t peer_idx, const uint8_t* stream, size_t len,
                              uint64_t* consumed, uint64_t* pushed, uint64_t* dropped) {
   if (!r || !consumed || (!stream && len)) return PBFT_EINVAL;
-  static thread_local char arena[1 << 16];  // unescaped strings (the PrePrepare's operation)
   uint64_t np = 0, nd = 0;
   size_t off = 0;
   int rc = 0;
@@ -2552,25 +2657,8 @@ int pbft_replica_push_frames(pbft_replica* r, uint32_t peer_idx, const uint8_t* 
     if (u != 0 || fl > PBFT_UVI_MAX_FRAME) { rc = PBFT_EINVAL; break; }
     if (len - off - hn < fl) break;  // incomplete frame: keep for the next read
     const char* js = (const char*)stream + off + hn;
-    pbft_wire_msg m;
-    const bool parsed = pbft_wire_decode_json(js, (size_t)fl, &m, arena, sizeof arena) == 0;
     off += hn + (size_t)fl;
-    int got = 0;
-    if (!parsed || !m.digest_ok || !m.has_sig) {
-      got = 0;  // not a signed PBFT message (the reference would panic in serde_json .unwrap(), src/message.rs:17-18)
-    } else if (m.kind == PBFT_MSG_PREPARE || m.kind == PBFT_MSG_COMMIT) {
-      // the signer is the authenticated connection (src/behavior.rs:346, :380), never the frame's field
-      if (m.replica != peer_idx) ++r->stats.rejected_signer;
-      else got = pbft_replica_push(r, (uint8_t)m.kind, m.view, m.seq, m.digest, peer_idx, m.sig);
-    } else if (m.kind == PBFT_MSG_PREPREPARE) {
-      // only on the primary's own connection (the reference receives it from the primary, src/behavior.rs:89-95):
-      // a relayed PrePrepare could otherwise fill the window's candidate slots ahead of the real one
-      const uint32_t p = r->n ? primary_of(r, m.view) : 0;
-      if (r->n == 0 || m.replica != p) ++r->stats.rejected_signer;
-      else  // (on_pre_prepare rejects a connection that is not the primary's)
-        got = pbft_replica_on_pre_prepare(r, peer_idx, m.view, m.seq, (const uint8_t*)m.operation, m.operation_len,
-                                          m.digest, m.sig, nullptr);
-    }
+    const int got = push_frame_body(r, peer_idx, js, (size_t)fl);
     if (got < 0) { rc = got; break; }
     if (got == 1) ++np; else ++nd;
   }
@@ -2620,6 +2708,328 @@ int pbft_replica_push_records(pbft_replica* r, uint32_t peer_idx, const uint8_t*
   if (pushed) *pushed = np;
   if (dropped) *dropped = nd;
   return rc;
+}
+
+// ---- every connection's bytes at once (include/pbft_replica.h pbft_replica_push_streams) ----
+// A forced flush whose events -- every queued one -- go to `ev`.
+static int flush_all(pbft_replica* r, std::vector<pbft_round_event>& ev) {
+  const int rc = pbft_replica_flush(r, 1, nullptr, 0, nullptr);
+  ev.insert(ev.end(), r->evq.begin(), r->evq.end());
+  r->evq.clear();
+  return rc;
+}
+
+// The sequence the call is defined by: flush, push_frames per segment, flush.
+static int streams_host_sequence(pbft_replica* r, const uint8_t* stream, const uint64_t* seg_off, const uint64_t* seg_len,
+                                 const uint16_t* seg_peer, uint32_t S, pbft_seg_head* heads, uint64_t* pushed,
+                                 uint64_t* dropped, std::vector<pbft_round_event>& ev) {
+  int rc = flush_all(r, ev);
+  if (rc) return rc;
+  uint64_t first = 0;
+  for (uint32_t s = 0; s < S; ++s) {
+    uint64_t used = 0, np = 0, nd = 0;
+    rc = pbft_replica_push_frames(r, seg_peer[s], stream + seg_off[s], (size_t)seg_len[s], &used, &np, &nd);
+    if (rc && rc != PBFT_EINVAL) return rc;  // (PBFT_EINVAL: a framing error, the segment's own)
+    heads[s].consumed = used;
+    heads[s].first = (uint32_t)first;
+    heads[s].n_frames = (uint32_t)(np + nd);
+    heads[s].status = rc ? PBFT_SEG_EFRAMING : PBFT_SEG_OK;
+    heads[s].pad = 0;
+    first += np + nd;
+    *pushed += np;
+    *dropped += nd;
+  }
+  return flush_all(r, ev);
+}
+
+// The front half on the host (a verifier override is installed): pbft_wire_frame_index per segment, the host builds
+// of wire_decode_core.h and admit_core.h, a dictionary for the grouping, the override for the bits, loops for the sets.
+// Fills r->front as pbft_verify_streams_admit does, except that nothing is cut at a cap: the caller compares the totals.
+static int streams_front_host(pbft_replica* r, const uint8_t* stream, const uint64_t* seg_off, const uint64_t* seg_len,
+                              const uint16_t* seg_peer, uint32_t S) {
+  StreamsFront& F = r->front;
+  std::vector<uint64_t> off;
+  std::vector<uint32_t> flen;
+  std::vector<uint16_t> peer;
+  for (uint32_t s = 0; s < S; ++s) {
+    const uint64_t cap = seg_len[s];  // (a frame takes at least one byte)
+    std::vector<uint64_t> o(cap);
+    std::vector<uint32_t> l(cap);
+    uint64_t n = 0, used = 0;
+    const int rc = pbft_wire_frame_index(stream + seg_off[s], (size_t)seg_len[s], cap, o.data(), l.data(), &n, &used);
+    pbft_seg_head& h = F.seg[s];
+    h.consumed = used;
+    h.first = (uint32_t)off.size();
+    h.n_frames = (uint32_t)n;
+    h.status = rc ? PBFT_SEG_EFRAMING : PBFT_SEG_OK;
+    h.pad = 0;
+    for (uint64_t f = 0; f < n; ++f) {
+      off.push_back(seg_off[s] + o[f]);
+      flen.push_back(l[f]);
+      peer.push_back(seg_peer[s]);
+    }
+  }
+  const uint64_t N = off.size();
+  F.n_frames[0] = (uint32_t)N;
+  F.n_frames[1] = 0;
+  // decode and classify
+  std::vector<pbft::admit_head> heads(N);
+  std::vector<uint8_t> rec((size_t)N * PBFT_RECORD_BYTES), cls(N);
+  for (uint64_t f = 0; f < N; ++f) {
+    uint32_t w[40];
+    pbft::frame_fields ff;
+    const pbft::frame_mem_reader rd{stream + off[f], 0, flen[f], 0};
+    pbft::wire_decode_frame(rd, 0, flen[f], r->n, peer[f], w, ff);
+    memcpy(&rec[(size_t)f * PBFT_RECORD_BYTES], w, PBFT_RECORD_BYTES);
+    heads[f] = pbft::admit_head{ff.view, ff.seq, (uint16_t)ff.key_idx, (uint8_t)ff.kind, (uint8_t)ff.status, flen[f]};
+  }
+  std::map<uint64_t, uint32_t> seen;  // admit_key -> rows (the planes, sparse)
+  for (uint64_t f = 0; f < N; ++f) {
+    cls[f] = (uint8_t)pbft::admit_classify(heads[f], f, N, r->current_view, r->h, r->log_window, r->n);
+    if (cls[f] == pbft::ADMIT_CLEAN) ++seen[pbft::admit_key(heads[f], r->h, r->n)];
+  }
+  memset(F.counts, 0, sizeof F.counts);
+  F.res.clear();
+  std::vector<uint64_t> clean_rows;
+  for (uint64_t f = 0; f < N; ++f) {
+    if (cls[f] == pbft::ADMIT_CLEAN && seen[pbft::admit_key(heads[f], r->h, r->n)] > 1) cls[f] = pbft::ADMIT_CONTESTED;
+    ++F.counts[cls[f]];
+    if (pbft::admit_is_residue(cls[f])) F.res.push_back(pbft_admit_residue{off[f], (uint32_t)f, flen[f]});
+    if (cls[f] == pbft::ADMIT_CLEAN) clean_rows.push_back(f);
+  }
+  F.n_res[0] = (uint32_t)F.res.size();
+  F.n_res[1] = 0;
+  // group the clean rows by envelope, verify them through the override, fold the two sets
+  const uint64_t C = clean_rows.size();
+  std::map<std::string, uint32_t> env_of;
+  std::vector<uint32_t> idx(C);
+  F.envelopes.clear();
+  for (uint64_t i = 0; i < C; ++i) {
+    const uint8_t* e = &rec[(size_t)clean_rows[i] * PBFT_RECORD_BYTES + 64];
+    auto it = env_of.emplace(std::string((const char*)e, PBFT_ENVELOPE_BYTES), (uint32_t)env_of.size());
+    if (it.second) F.envelopes.insert(F.envelopes.end(), e, e + PBFT_ENVELOPE_BYTES);
+    idx[i] = it.first->second;
+  }
+  F.n_env[0] = (uint32_t)env_of.size();
+  F.n_env[1] = 0;
+  F.W = (r->n + 63) / 64;
+  F.present.assign((size_t)F.n_env[0] * F.W, 0);
+  F.valid.assign((size_t)F.n_env[0] * F.W, 0);
+  if (C) {
+    std::vector<uint8_t> R(32 * C), Sg(32 * C), M(PBFT_ENVELOPE_BYTES * C + 16, 0);
+    std::vector<uint16_t> K(C);
+    std::vector<uint64_t> bits((C + 63) / 64, 0);
+    for (uint64_t i = 0; i < C; ++i) {
+      const uint8_t* q = &rec[(size_t)clean_rows[i] * PBFT_RECORD_BYTES];
+      memcpy(&R[32 * i], q, 32);
+      memcpy(&Sg[32 * i], q + 32, 32);
+      memcpy(&M[PBFT_ENVELOPE_BYTES * i], q + 64, PBFT_ENVELOPE_BYTES);
+      K[i] = heads[clean_rows[i]].key_idx;
+    }
+    const int rc = r->verify_fn(r->verify_user, R.data(), Sg.data(), K.data(), M.data(), PBFT_ENVELOPE_BYTES,
+                                PBFT_ENVELOPE_BYTES, C, bits.data());
+    if (rc) return rc;
+    for (uint64_t i = 0; i < C; ++i) {
+      const size_t at = (size_t)idx[i] * F.W + K[i] / 64;
+      F.present[at] |= (uint64_t)1 << (K[i] & 63);
+      if ((bits[i >> 6] >> (i & 63)) & 1) F.valid[at] |= (uint64_t)1 << (K[i] & 63);
+    }
+  }
+  return PBFT_OK;
+}
+
+// A frame of the residue may be a vote in a form the frame decoder defers (whitespace, another field order): the
+// per-frame code pushes it like any other.  If a clean row of the same call has its (kind, seq, signer), the two would
+// meet in one phase (a repeated vote is a duplicate, a second digest a second candidate) and the clean row is not
+// independent of the residue after all: the caller then takes the host sequence.  A correct peer sends the canonical
+// form only.
+static bool streams_residue_conflict(pbft_replica* r, const uint8_t* stream, uint64_t stream_bytes,
+                                     const uint16_t* seg_peer, uint32_t S) {
+  const StreamsFront& F = r->front;
+  if (!F.n_res[0] || !F.n_env[0]) return false;
+  std::map<std::pair<uint8_t, uint64_t>, std::vector<uint64_t>> have;  // (kind, seq) -> signers of its clean rows
+  for (uint32_t e = 0; e < F.n_env[0]; ++e) {
+    const uint8_t* env = &F.envelopes[(size_t)e * PBFT_ENVELOPE_BYTES];
+    uint64_t seq;
+    memcpy(&seq, env + 13, 8);
+    std::vector<uint64_t>& set = have[{env[4], seq}];
+    set.resize(F.W, 0);
+    for (uint32_t w = 0; w < F.W; ++w) set[w] |= F.present[(size_t)e * F.W + w];
+  }
+  static thread_local char arena[1 << 16];
+  uint32_t s = 0;
+  for (uint32_t i = 0; i < F.n_res[0]; ++i) {
+    const pbft_admit_residue& e = F.res[i];
+    while (s < S && e.frame >= F.seg[s].first + F.seg[s].n_frames) ++s;
+    if (s >= S || e.off > stream_bytes || e.len > stream_bytes - e.off) return true;  // (the host sequence decides)
+    pbft_wire_msg m;
+    if (pbft_wire_decode_json((const char*)stream + e.off, e.len, &m, arena, sizeof arena) != 0 || !m.digest_ok ||
+        !m.has_sig || (m.kind != PBFT_MSG_PREPARE && m.kind != PBFT_MSG_COMMIT) || m.replica != seg_peer[s] ||
+        m.view != r->current_view)
+      continue;
+    const auto it = have.find({(uint8_t)m.kind, m.seq});
+    if (it != have.end() && (it->second[m.replica / 64] >> (m.replica & 63)) & 1) return true;
+  }
+  return false;
+}
+
+// The front half on the replica's GPU context.
+static int streams_front_device(pbft_replica* r, const uint8_t* stream, uint64_t stream_bytes, const uint64_t* seg_off,
+                                const uint64_t* seg_len, const uint16_t* seg_peer, uint32_t S) {
+  StreamsFront& F = r->front;
+  F.W = (r->n + 63) / 64;
+  F.envelopes.resize((size_t)F.env_cap * PBFT_ENVELOPE_BYTES);
+  F.present.resize((size_t)F.env_cap * F.W);
+  F.valid.resize((size_t)F.env_cap * F.W);
+  F.res.resize(F.residue_cap);
+  if (!pbft_verify_streams_admit) return PBFT_ENODEV;
+  return pbft_verify_streams_admit(r->ctx, stream, stream_bytes, seg_off, seg_len, seg_peer, S, r->n, F.frame_cap,
+                                   F.env_cap, F.residue_cap, r->current_view, r->h, r->log_window, F.seg.data(),
+                                   F.n_frames, F.counts, F.envelopes.data(), F.n_env, F.present.data(), F.valid.data(),
+                                   F.res.data(), F.n_res);
+}
+
+int pbft_replica_push_streams(pbft_replica* r, const uint8_t* stream, uint64_t stream_bytes, const uint64_t* seg_off,
+                              const uint64_t* seg_len, const uint16_t* seg_peer, uint32_t S, pbft_seg_head* heads,
+                              uint64_t* pushed, uint64_t* dropped, pbft_round_event* events, uint32_t max_events,
+                              uint32_t* n_events) {
+  if (!r || (!stream && stream_bytes) || (S && (!seg_off || !seg_len || !seg_peer || !heads)) || !pushed || !dropped ||
+      (max_events && !events) || !n_events)
+    return PBFT_EINVAL;
+  if (S > 65536 || stream_bytes > ((uint64_t)1 << 31)) return PBFT_EINVAL;
+  uint64_t sum = 0;
+  for (uint32_t s = 0; s < S; ++s) {
+    if (seg_peer[s] >= r->n || seg_len[s] > stream_bytes || seg_off[s] > stream_bytes - seg_len[s]) return PBFT_EINVAL;
+    sum += seg_len[s];
+  }
+  if (sum > stream_bytes) return PBFT_EINVAL;
+  if (r->in_flight) return PBFT_EBUSY;
+  if (!r->verify_fn && !r->vsub && !r->ctx) return PBFT_ENODEV;
+  *pushed = *dropped = 0;
+  *n_events = 0;
+  std::vector<pbft_round_event> ev;
+  StreamsFront& F = r->front;
+  uint64_t* why = nullptr;  // the whole-call fallback's counter
+  int rc = PBFT_OK;
+  if (r->ctxs.size() > 1) why = &r->sstats.fallback_multi;
+  else if (pbft::admit_plane_bits(r->log_window, r->n) == 0) why = &r->sstats.fallback_planes;
+  else if (!r->verify_fn && r->vsub) why = &r->sstats.fallback_verifier;
+  if (!why) {
+    // 1. candidates pending at entry never meet this call's rows in one batch
+    if ((rc = flush_all(r, ev)) != PBFT_OK) return rc;
+    // 2. the front half: pure, nothing of the replica changes
+    const auto t0 = std::chrono::steady_clock::now();
+    F.seg.assign(S, pbft_seg_head{});
+    rc = r->verify_fn ? streams_front_host(r, stream, seg_off, seg_len, seg_peer, S)
+                      : streams_front_device(r, stream, stream_bytes, seg_off, seg_len, seg_peer, S);
+    r->sstats.front_ns += ns_since(t0);
+    if (rc) { r->evq.insert(r->evq.begin(), ev.begin(), ev.end()); return rc; }  // (the events stay queued)
+    if (F.n_frames[0] > F.frame_cap) why = &r->sstats.fallback_frames;
+    else if (F.n_env[0] > F.env_cap) why = &r->sstats.fallback_envelopes;
+    else if (F.n_res[0] > F.residue_cap) why = &r->sstats.fallback_residue;
+    else if (streams_residue_conflict(r, stream, stream_bytes, seg_peer, S)) why = &r->sstats.fallback_deferred;
+  }
+  if (why) {
+    ++*why;
+    rc = streams_host_sequence(r, stream, seg_off, seg_len, seg_peer, S, heads, pushed, dropped, ev);
+  } else {
+    ++(r->verify_fn ? r->sstats.calls_host_front : r->sstats.calls_device);
+    for (uint32_t s = 0; s < S; ++s) heads[s] = F.seg[s];
+    // 3. the rows the device counted and dropped: what the push of each would have counted
+    const uint64_t rv = F.counts[pbft::ADMIT_REJ_VIEW], rw = F.counts[pbft::ADMIT_REJ_WATERMARK],
+                   rs = F.counts[pbft::ADMIT_REJ_SIGNER];
+    r->stats.rejected_view += rv;
+    r->stats.rejected_watermark += rw;
+    r->stats.rejected_signer += rs;
+    r->stats.pushed += rv + rw;
+    *dropped += rv + rw + rs;
+    // 4. the residue, in frame order, through push_frames' own per-frame code
+    uint32_t s = 0;
+    for (uint32_t i = 0; i < F.n_res[0] && rc >= 0; ++i) {
+      const pbft_admit_residue& e = F.res[i];
+      while (s < S && e.frame >= F.seg[s].first + F.seg[s].n_frames) ++s;
+      if (s >= S || e.off > stream_bytes || e.len > stream_bytes - e.off) { rc = PBFT_EINVAL; break; }
+      const int got = push_frame_body(r, seg_peer[s], (const char*)stream + e.off, e.len);
+      if (got < 0) rc = got;
+      else if (got == 1) ++*pushed;
+      else ++*dropped;
+    }
+    if (rc > 0) rc = PBFT_OK;
+    // 5. the clean votes, per envelope: a late or repeated vote is a duplicate now, as its push would find; the rest
+    //    wait as two signer sets for the flush below
+    const uint32_t n_env = F.n_env[0];
+    for (uint32_t e = 0; e < n_env && rc == PBFT_OK; ++e) {
+      const uint8_t* env = &F.envelopes[(size_t)e * PBFT_ENVELOPE_BYTES];
+      PendingSet ps;
+      ps.kind = env[4];
+      uint64_t view;
+      memcpy(&view, env + 5, 8);
+      memcpy(&ps.seq, env + 13, 8);
+      memcpy(ps.digest.data(), env + 21, 64);
+      if (memcmp(env, "PBFT", 4) != 0 || (ps.kind != 1 && ps.kind != 2) || view != r->current_view ||
+          !in_log(r, ps.seq)) { rc = PBFT_EINVAL; break; }  // (not what the admission pass lets through)
+      ps.present.assign(&F.present[(size_t)e * F.W], &F.present[(size_t)e * F.W] + F.W);
+      ps.valid.assign(&F.valid[(size_t)e * F.W], &F.valid[(size_t)e * F.W] + F.W);
+      Window& w = window_at(r, ps.seq);  // (created for `present`, as a push would create it)
+      Phase& p = w.ph[ps.kind];
+      p.init(r->n);
+      uint64_t left = 0;
+      for (uint32_t wi = 0; wi < F.W; ++wi) {
+        for (uint64_t m = ps.present[wi]; m; m &= m - 1) {
+          const uint32_t sg = 64 * wi + (uint32_t)__builtin_ctzll(m);
+          ++r->stats.pushed;
+          ++r->sstats.clean_rows;
+          const bool dup = sg >= r->n || w.committed_reported ||
+                           (p.acc[sg] && p.acc_digs[p.acc[sg] - 1] == ps.digest);
+          if (dup) {
+            ++r->stats.duplicates;
+            ++*dropped;
+            ps.present[wi] &= ~((uint64_t)1 << (sg & 63));
+          } else {
+            ++*pushed;
+          }
+        }
+        left |= ps.present[wi];
+      }
+      if (left) r->pend.push_back(std::move(ps));
+    }
+    r->sstats.residue_rows += F.n_res[0];
+    r->sstats.envelopes += n_env;
+    r->defer_eval = !r->pend.empty();
+    // 6. the forced flush: the residue's batch, then the sets, then the windows' events and the GC, once
+    const int rf = flush_all(r, ev);
+    if (rc == PBFT_OK) rc = rf;
+  }
+  std::stable_sort(ev.begin(), ev.end(), [](const pbft_round_event& a, const pbft_round_event& b) {
+    return std::tie(a.view, a.seq, a.kind) < std::tie(b.view, b.seq, b.kind);
+  });
+  uint32_t ne = 0;
+  for (; ne < max_events && ne < ev.size(); ++ne) events[ne] = ev[ne];
+  r->evq.insert(r->evq.begin(), ev.begin() + ne, ev.end());  // (the rest wait for the next flush / flush_poll)
+  *n_events = ne;
+  return rc;
+}
+
+int pbft_replica_reserve_streams(pbft_replica* r, uint64_t max_stream_bytes, uint32_t max_segments, uint64_t frame_cap,
+                                 uint32_t env_cap, uint32_t residue_cap) {
+  if (!r || frame_cap == 0 || frame_cap > ((uint64_t)1 << 31) || env_cap == 0 || max_segments > 65536 ||
+      max_stream_bytes > ((uint64_t)1 << 31))
+    return PBFT_EINVAL;
+  if (r->in_flight) return PBFT_EBUSY;
+  r->front.frame_cap = frame_cap;
+  r->front.env_cap = env_cap;
+  r->front.residue_cap = residue_cap;
+  if (!r->ctx || r->ctxs.size() > 1 || r->verify_fn || r->vsub || pbft::admit_plane_bits(r->log_window, r->n) == 0)
+    return PBFT_OK;  // (no device front half to size)
+  if (!pbft_streams_admit_reserve) return PBFT_ENODEV;
+  return pbft_streams_admit_reserve(r->ctx, max_stream_bytes, max_segments, r->n, frame_cap, env_cap, residue_cap,
+                                    r->log_window);
+}
+
+int pbft_replica_get_streams_stats(pbft_replica* r, pbft_replica_streams_stats* out) {
+  if (!r || !out) return PBFT_EINVAL;
+  *out = r->sstats;
+  return PBFT_OK;
 }
 
 int pbft_replica_stable_checkpoint(pbft_replica* r, uint64_t seq) {

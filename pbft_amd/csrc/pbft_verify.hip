@@ -35,6 +35,7 @@
 using namespace pbft;
 #include "verify_kernels.h"
 #include "tally_kernels.h"
+#include "admit_kernels.h"
 #include "group_kernels.h"
 #include "wire_decode_kernels.h"
 #include "wire_index_kernels.h"
@@ -255,6 +256,9 @@ struct pbft_ctx {
   uint8_t* d_index = nullptr;
   size_t index_cap = 0;  // bytes
   uint32_t index_tile = INDEX_TILE_DEFAULT;
+  // pbft_admit_device: the two key planes, the residue marks and their prefix (grow-only; pbft_admit_reserve)
+  uint8_t* d_admit = nullptr;
+  size_t admit_cap = 0;  // bytes
 };
 
 #ifndef PBFT_ENV_SCHED
@@ -1036,6 +1040,7 @@ int pbft_verify_ctx_destroy(pbft_ctx* c) {
   (void)hipFree(c->d_fpatch);
   (void)hipFree(c->d_group);
   (void)hipFree(c->d_index);
+  (void)hipFree(c->d_admit);
   if (c->h_bitmap) (void)hipHostFree(c->h_bitmap);
   if (c->h_stage) (void)hipHostFree(c->h_stage);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -2346,6 +2351,66 @@ int pbft_verify_frames_tally(pbft_ctx* c, const uint8_t* stream, uint64_t stream
   return PBFT_OK;
 }
 
+// ---- the replica's admission pass (include/pbft_wire.h; kernels: admit.hip) ----
+static_assert(sizeof(pbft_frame_head) == sizeof(pbft::admit_head) && sizeof(pbft_admit_residue) == sizeof(admit_residue),
+              "admit.hip reads pbft_frame_head and writes pbft_admit_residue");
+static_assert(PBFT_ADMIT_CLEAN == pbft::ADMIT_CLEAN && PBFT_ADMIT_CONTESTED == pbft::ADMIT_CONTESTED &&
+                  PBFT_ADMIT_REJ_VIEW == pbft::ADMIT_REJ_VIEW && PBFT_ADMIT_REJ_WATERMARK == pbft::ADMIT_REJ_WATERMARK &&
+                  PBFT_ADMIT_REJ_SIGNER == pbft::ADMIT_REJ_SIGNER && PBFT_ADMIT_HOST == pbft::ADMIT_HOST &&
+                  PBFT_ADMIT_PAD == pbft::ADMIT_PAD && PBFT_ADMIT_CLASSES == pbft::ADMIT_CLASSES,
+              "PBFT_ADMIT_* are admit_core.h's classes");
+static int ensure_admit(pbft_ctx* c, uint64_t plane_bits, uint64_t N) {
+  const size_t bytes = admit_ws(plane_bits, N).total;
+  if (bytes <= c->admit_cap) return PBFT_OK;
+  if (c->d_admit) HIP_TRY(hipFree(c->d_admit));  // (waits for the device: an earlier call may still use it)
+  c->d_admit = nullptr;
+  c->admit_cap = 0;
+  if (hipMalloc(&c->d_admit, bytes) != hipSuccess) return set_err(PBFT_ENOMEM, "admit workspace alloc");
+  c->admit_cap = bytes;
+  return PBFT_OK;
+}
+
+static int check_admit_shape(uint64_t log_window, uint32_t n_keys, uint64_t N) {
+  if (N > ADMIT_MAX_ROWS) return set_err(PBFT_EINVAL, "more than 2^31 rows to admit");
+  if (n_keys == 0 || n_keys > 65535) return set_err(PBFT_EINVAL, "n_keys out of range");
+  if (log_window == 0 || pbft::admit_plane_bits(log_window, n_keys) == 0)
+    return set_err(PBFT_EINVAL, "2 * log_window * n_keys must be in [1, 2^30]");
+  return PBFT_OK;
+}
+
+// Five launches on the caller's stream.  The workspace grows here only when the call is larger than every one before
+// it and than pbft_admit_reserve.
+int pbft_admit_device(pbft_ctx* c, const pbft_frame_head* d_heads, uint8_t* d_records, const uint64_t* d_off,
+                      const uint32_t* d_len, const uint32_t* d_n_frames, uint64_t N, uint64_t view, uint64_t h,
+                      uint64_t log_window, uint32_t n_keys, uint32_t residue_cap, uint8_t* d_class, uint32_t* d_counts,
+                      uint64_t* d_clean, pbft_admit_residue* d_res, uint32_t* d_n_res, void* stream) {
+  if (!c) return set_err(PBFT_EINVAL, "null context");
+  int rc = check_admit_shape(log_window, n_keys, N);
+  if (rc) return rc;
+  if (!d_counts || !d_n_res || (N && (!d_heads || !d_records || !d_class || !d_clean)) || (residue_cap && !d_res))
+    return set_err(PBFT_EINVAL, "null admit argument");
+  if (((uintptr_t)d_heads & 7) || ((uintptr_t)d_records & 1) || ((uintptr_t)d_off & 7) || ((uintptr_t)d_len & 3) ||
+      ((uintptr_t)d_n_frames & 3) || ((uintptr_t)d_counts & 3) || ((uintptr_t)d_clean & 7) || ((uintptr_t)d_res & 7) ||
+      ((uintptr_t)d_n_res & 3))
+    return set_err(PBFT_EINVAL, "misaligned admit pointer");
+  HIP_TRY(hipSetDevice(c->device));
+  rc = ensure_admit(c, pbft::admit_plane_bits(log_window, n_keys), N);
+  if (rc) return rc;
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  HIP_TRY(launch_admit((const pbft::admit_head*)d_heads, d_records, d_off, d_len, d_n_frames, N, view, h, log_window,
+                       n_keys, residue_cap, c->d_admit, d_class, d_counts, d_clean, (admit_residue*)d_res, d_n_res,
+                       st));
+  return PBFT_OK;
+}
+
+int pbft_admit_reserve(pbft_ctx* c, uint64_t log_window, uint32_t n_keys, uint64_t max_n) {
+  if (!c) return set_err(PBFT_EINVAL, "null context");
+  const int rc = check_admit_shape(log_window, n_keys, max_n);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  return ensure_admit(c, pbft::admit_plane_bits(log_window, n_keys), max_n);
+}
+
 // ---- connection streams in: the frame index made on the device (include/pbft_wire.h; kernels: wire_index.hip) ----
 static_assert(sizeof(pbft_seg_head) == 24, "pbft_seg_head is 24 bytes");
 static int ensure_index(pbft_ctx* c, uint64_t stream_bytes, uint32_t S) {
@@ -2550,6 +2615,138 @@ int pbft_verify_streams_tally(pbft_ctx* c, const uint8_t* stream, uint64_t strea
   HIP_TRY(hipMemcpyAsync(signers_out, d + o_set, set_bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipMemcpyAsync(count_out, d + o_cnt, cnt_bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  return PBFT_OK;
+}
+
+// ---- connection streams in, signer sets out: the device half of pbft_replica_push_streams ----
+// One staging, one enqueue of the whole chain over N = frame_cap rows (the index pads what the streams do not fill),
+// one synchronisation.
+struct admit_layout {
+  frames_layout lay;
+  uint32_t W;
+  size_t env_bytes, set_bytes, o_soff, o_slen, o_shead, o_nfr, o_speer, o_idx, o_env, o_n, o_present, o_valid, o_cnt,
+      o_cls, o_counts, o_clean, o_res, o_nres, total;
+  admit_layout(uint64_t stream_bytes, uint32_t S, uint64_t frame_cap, uint32_t env_cap, uint32_t residue_cap,
+               uint32_t n_replicas)
+      : lay(frame_cap, stream_bytes) {
+    auto up = [](size_t x) { return (x + 15) & ~(size_t)15; };
+    W = tally_words(n_replicas);
+    env_bytes = (size_t)env_cap * PBFT_ENVELOPE_LEN;
+    set_bytes = (size_t)env_cap * W * 8;
+    o_soff = up(lay.total);
+    o_slen = o_soff + 8 * (size_t)S;
+    o_shead = o_slen + 8 * (size_t)S;
+    o_nfr = o_shead + sizeof(pbft_seg_head) * (size_t)S;
+    o_speer = o_nfr + 8;
+    o_idx = up(o_speer + 2 * (size_t)S);
+    o_env = o_idx + up(4 * (size_t)frame_cap);
+    o_n = o_env + up(env_bytes + 16);
+    o_present = o_n + 16;
+    o_valid = o_present + up(set_bytes);
+    o_cnt = o_valid + up(set_bytes);
+    o_cls = o_cnt + up(4 * (size_t)env_cap);
+    o_counts = o_cls + up((size_t)frame_cap);
+    o_clean = o_counts + 32;
+    o_res = o_clean + up(8 * (((size_t)frame_cap + 63) / 64));
+    o_nres = o_res + sizeof(pbft_admit_residue) * (size_t)residue_cap;
+    total = o_nres + 16 + 256;
+  }
+};
+
+static int check_streams_admit_shape(pbft_ctx* c, uint64_t stream_bytes, uint32_t S, uint32_t n_replicas,
+                                     uint64_t frame_cap, uint32_t env_cap, uint64_t log_window) {
+  if (!c) return set_err(PBFT_EINVAL, "null context");
+  if (n_replicas == 0 || n_replicas > 65535) return set_err(PBFT_EINVAL, "n_replicas out of range");
+  if (S > pbft::IX_MAX_SEGMENTS) return set_err(PBFT_EINVAL, "more than 65536 segments");
+  if (frame_cap == 0 || frame_cap > ((uint64_t)1 << 31)) return set_err(PBFT_EINVAL, "frame_cap out of range");
+  if (env_cap == 0) return set_err(PBFT_EINVAL, "env_cap is 0");
+  if (stream_bytes > pbft::IX_MAX_STREAM) return set_err(PBFT_EINVAL, "more than 2^31 stream bytes to index");
+  return check_admit_shape(log_window, n_replicas, frame_cap);
+}
+
+int pbft_streams_admit_reserve(pbft_ctx* c, uint64_t max_stream_bytes, uint32_t max_segments, uint32_t n_replicas,
+                               uint64_t frame_cap, uint32_t env_cap, uint32_t residue_cap, uint64_t log_window) {
+  int rc = check_streams_admit_shape(c, max_stream_bytes, max_segments, n_replicas, frame_cap, env_cap, log_window);
+  if (rc) return rc;
+  if (c->in_flight) return set_err(PBFT_EBUSY, "async batch in flight");
+  HIP_TRY(hipSetDevice(c->device));
+  const admit_layout L(max_stream_bytes, max_segments, frame_cap, env_cap, residue_cap, n_replicas);
+  if ((rc = ensure_stage(c, L.total, (frame_cap + 63) / 64)) != PBFT_OK) return rc;
+  if ((rc = ensure_index(c, max_stream_bytes, max_segments)) != PBFT_OK) return rc;
+  if ((rc = ensure_group(c, frame_cap)) != PBFT_OK) return rc;
+  if ((rc = ensure_admit(c, pbft::admit_plane_bits(log_window, n_replicas), frame_cap)) != PBFT_OK) return rc;
+  return ensure_work(c, frame_cap, true);
+}
+
+int pbft_verify_streams_admit(pbft_ctx* c, const uint8_t* stream, uint64_t stream_bytes, const uint64_t* seg_off,
+                              const uint64_t* seg_len, const uint16_t* seg_peer, uint32_t S, uint32_t n_replicas,
+                              uint64_t frame_cap, uint32_t env_cap, uint32_t residue_cap, uint64_t view, uint64_t h,
+                              uint64_t log_window, pbft_seg_head* seg_heads_out, uint32_t* n_frames_out,
+                              uint32_t* counts_out, uint8_t* envelopes_out, uint32_t* n_env_out, uint64_t* present_out,
+                              uint64_t* valid_out, pbft_admit_residue* res_out, uint32_t* n_res_out) {
+  int rc = check_streams_admit_shape(c, stream_bytes, S, n_replicas, frame_cap, env_cap, log_window);
+  if (rc) return rc;
+  if (c->in_flight) return set_err(PBFT_EBUSY, "async batch in flight");
+  if (!n_frames_out || !counts_out || !envelopes_out || !n_env_out || !present_out || !valid_out || !n_res_out ||
+      (residue_cap && !res_out) || (stream_bytes && !stream) || (S && (!seg_off || !seg_len || !seg_peer || !seg_heads_out)))
+    return set_err(PBFT_EINVAL, "null streams argument");
+  if (c->n_keys < n_replicas) return set_err(PBFT_ENOKEYS, "fewer keys installed than replicas");
+  HIP_TRY(hipSetDevice(c->device));
+  const admit_layout L(stream_bytes, S, frame_cap, env_cap, residue_cap, n_replicas);
+  rc = ensure_stage(c, L.total, (frame_cap + 63) / 64);
+  if (rc) return rc;
+  uint8_t* const d = c->d_stage;
+  const uint64_t N = frame_cap;
+  pbft_frame_head* const d_heads = (pbft_frame_head*)(d + L.lay.heads);
+  uint64_t* const d_off = (uint64_t*)(d + L.lay.off);
+  uint32_t* const d_len = (uint32_t*)(d + L.lay.len);
+  uint16_t* const d_peer = (uint16_t*)(d + L.lay.peer);
+  uint32_t* const d_nfr = (uint32_t*)(d + L.o_nfr);
+  uint32_t* const d_idx = (uint32_t*)(d + L.o_idx);
+  const uint16_t* const d_key = (const uint16_t*)(d + 150);
+  uint64_t* const d_clean = (uint64_t*)(d + L.o_clean);
+  hipStream_t st = c->stream;
+  if (stream_bytes) HIP_TRY(hipMemcpyAsync(d + L.lay.stream, stream, stream_bytes, hipMemcpyHostToDevice, st));
+  if (S) {
+    HIP_TRY(hipMemcpyAsync(d + L.o_soff, seg_off, 8 * (size_t)S, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d + L.o_slen, seg_len, 8 * (size_t)S, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d + L.o_speer, seg_peer, 2 * (size_t)S, hipMemcpyHostToDevice, st));
+  }
+  // with S = 0 the index still pads every row; its peer pointers must then both be null or both set: a dummy table
+  rc = pbft_wire_index_streams_device(c, d + L.lay.stream, stream_bytes, (const uint64_t*)(d + L.o_soff),
+                                      (const uint64_t*)(d + L.o_slen), (const uint16_t*)(d + L.o_speer), S, N, d_off,
+                                      d_len, d_peer, (pbft_seg_head*)(d + L.o_shead), d_nfr, st);
+  if (rc) return rc;
+  rc = pbft_wire_decode_frames_device(c, d + L.lay.stream, stream_bytes, d_off, d_len, d_peer, n_replicas, N, d,
+                                      d_heads, st);
+  if (rc) return rc;
+  rc = pbft_admit_device(c, d_heads, d, d_off, d_len, d_nfr, N, view, h, log_window, n_replicas, residue_cap,
+                         d + L.o_cls, (uint32_t*)(d + L.o_counts), d_clean, (pbft_admit_residue*)(d + L.o_res),
+                         (uint32_t*)(d + L.o_nres), st);
+  if (rc) return rc;
+  rc = pbft_group_envelopes_device(c, d + 64, PBFT_RECORD_BYTES, d_key, PBFT_RECORD_BYTES, N, env_cap, d_idx,
+                                   d + L.o_env, (uint32_t*)(d + L.o_n), st);
+  if (rc) return rc;
+  rc = pbft_verify_records_device(c, d, N, c->d_bitmap, st);
+  if (rc) return rc;
+  rc = pbft_tally_device(c, d_clean, d_key, PBFT_RECORD_BYTES, d_idx, 4, N, env_cap, n_replicas, 0,
+                         (uint64_t*)(d + L.o_present), (uint32_t*)(d + L.o_cnt), st);
+  if (rc) return rc;
+  rc = pbft_tally_device(c, c->d_bitmap, d_key, PBFT_RECORD_BYTES, d_idx, 4, N, env_cap, n_replicas, 0,
+                         (uint64_t*)(d + L.o_valid), (uint32_t*)(d + L.o_cnt), st);
+  if (rc) return rc;
+  if (S) HIP_TRY(hipMemcpyAsync(seg_heads_out, d + L.o_shead, sizeof(pbft_seg_head) * (size_t)S, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(n_frames_out, d_nfr, 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(counts_out, d + L.o_counts, 32, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(envelopes_out, d + L.o_env, L.env_bytes, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(n_env_out, d + L.o_n, 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(present_out, d + L.o_present, L.set_bytes, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(valid_out, d + L.o_valid, L.set_bytes, hipMemcpyDeviceToHost, st));
+  if (residue_cap)
+    HIP_TRY(hipMemcpyAsync(res_out, d + L.o_res, sizeof(pbft_admit_residue) * (size_t)residue_cap,
+                           hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(n_res_out, d + L.o_nres, 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
   return PBFT_OK;
 }
 

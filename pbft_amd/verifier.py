@@ -131,6 +131,62 @@ def group_reference(msg_rows, skip_mask, env_cap: int):
     return env_idx, envelopes, np.array([len(seen), lost], dtype=np.uint32)
 
 
+ADMIT_CLEAN, ADMIT_CONTESTED, ADMIT_REJ_VIEW, ADMIT_REJ_WATERMARK, ADMIT_REJ_SIGNER, ADMIT_HOST, ADMIT_PAD = range(7)
+ADMIT_CLASSES = 8  # PBFT_ADMIT_* (include/pbft_wire.h)
+
+
+def admit_reference(heads, view: int, h: int, log_window: int, n_keys: int, residue_cap: int, n_total=None,
+                    off=None, flen=None) -> dict:
+    """The semantics of pbft_admit_device in plain Python over a wire.FrameHead array: what the replica does with
+    each decoded frame before it touches a round window.  Frame f >= min(n_total, N) is ADMIT_PAD; status ESIGNER (5)
+    is ADMIT_REJ_SIGNER; any other status but OK, and kind 0, is ADMIT_HOST; an OK vote whose key index is >= n_keys
+    is ADMIT_REJ_SIGNER, of another view ADMIT_REJ_VIEW (tested before the window), with seq outside (h, h +
+    log_window] ADMIT_REJ_WATERMARK (integers: h + log_window may pass 2^64, the window then ends at 2^64 - 1); what
+    is left is admitted, ADMIT_CONTESTED if another admitted row has its (kind, seq, signer), else ADMIT_CLEAN.
+    Returns cls (N,) uint8, counts (8,) uint32, clean (ceil(N / 64),) uint64 bitmap, res (residue_cap,) wire.AdmitResidue
+    = the CONTESTED and HOST frames in frame order (zeros behind; off / len from `off` / `flen`, 0 without them),
+    n_res (2,) uint32 = [their number, those residue_cap left out], and keep (N,) bool = the rows whose record keeps
+    its key index (the others get 0xFFFF)."""
+    from .wire import AdmitResidue
+    n = len(heads)
+    n_valid = n if n_total is None else min(int(n_total), n)
+    cls = np.zeros(n, dtype=np.uint8)
+    seen: dict = {}
+    for f in range(n):
+        hd = heads[f]
+        st, kind, key = int(hd["status"]), int(hd["kind"]), int(hd["key_idx"])
+        if f >= n_valid:
+            c = ADMIT_PAD
+        elif st == 5:
+            c = ADMIT_REJ_SIGNER
+        elif st != 0 or kind not in (1, 2):
+            c = ADMIT_HOST
+        elif key >= n_keys:
+            c = ADMIT_REJ_SIGNER
+        elif int(hd["view"]) != view:
+            c = ADMIT_REJ_VIEW
+        elif not (h < int(hd["seq"]) <= h + log_window):
+            c = ADMIT_REJ_WATERMARK
+        else:
+            c = ADMIT_CLEAN
+            seen.setdefault((kind, int(hd["seq"]), key), []).append(f)
+        cls[f] = c
+    for rows in seen.values():
+        if len(rows) > 1:
+            cls[rows] = ADMIT_CONTESTED
+    counts = np.bincount(cls, minlength=ADMIT_CLASSES).astype(np.uint32)
+    keep = cls == ADMIT_CLEAN
+    bits = np.zeros((n + 63) // 64 * 64, dtype=np.uint8)
+    bits[:n] = keep
+    clean = np.packbits(bits, bitorder="little").view(np.uint64) if n else np.zeros(0, np.uint64)
+    res = np.zeros(residue_cap, dtype=AdmitResidue)
+    frames = np.flatnonzero((cls == ADMIT_CONTESTED) | (cls == ADMIT_HOST))
+    for at, f in enumerate(frames[:residue_cap]):
+        res[at] = (0 if off is None else int(off[f]), f, 0 if flen is None else int(flen[f]))
+    n_res = np.array([len(frames), max(0, len(frames) - residue_cap)], dtype=np.uint32)
+    return dict(cls=cls, counts=counts, clean=clean, res=res, n_res=n_res, keep=keep)
+
+
 def quorum(counts, need: int) -> np.ndarray:
     """Envelopes with at least `need` distinct valid signers (2f for prepared, 2f + 1 for committed-local:
     src/behavior.rs:177-182, :214-223); bool per envelope."""
@@ -552,6 +608,21 @@ class GpuBatchVerifier:
         if want_index:
             res.update(off=off[:n], flen=flen[:n])
         return res
+
+    def admit_reserve(self, log_window: int, n_keys: int, max_n: int) -> None:
+        """pbft_admit_reserve: pre-size the admission workspace (required before capturing admit_device)."""
+        check(self._lib.pbft_admit_reserve(self._ctx, log_window, n_keys, max_n))
+
+    def admit_device(self, d_heads: int, d_records: int, n: int, view: int, h: int, log_window: int, n_keys: int,
+                     residue_cap: int, d_class: int, d_counts: int, d_clean: int, d_res: int, d_n_res: int,
+                     d_off: int = 0, d_len: int = 0, d_n_frames: int = 0, stream: int = 0) -> None:
+        """pbft_admit_device: enqueue the replica's admission pass over n decoded frames (raw device pointers): class
+        per frame, class counts, clean bitmap, residue list, and key index 0xFFFF into the record of every frame
+        that is not clean -- see admit_reference."""
+        check(self._lib.pbft_admit_device(self._ctx, d_heads or None, d_records or None, d_off or None, d_len or None,
+                                          d_n_frames or None, n, view, h, log_window, n_keys, residue_cap,
+                                          d_class or None, d_counts or None, d_clean or None, d_res or None,
+                                          d_n_res or None, stream or None))
 
     OPT_INDEX_TILE = 19
     OPT_GROUP_SEED, OPT_GROUP_HASH_BITS = 16, 17

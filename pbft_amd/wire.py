@@ -27,6 +27,9 @@ assert FrameHead.itemsize == 24
 # pbft_seg_head (include/pbft_wire.h): one per segment of index_streams_device / verify_streams_tally
 SegHead = np.dtype([("consumed", "<u8"), ("first", "<u4"), ("n_frames", "<u4"), ("status", "<u4"), ("pad", "<u4")])
 assert SegHead.itemsize == 24
+# pbft_admit_residue (include/pbft_wire.h): one frame the replica's host code has to see, 16 bytes
+AdmitResidue = np.dtype([("off", "<u8"), ("frame", "<u4"), ("len", "<u4")])
+assert AdmitResidue.itemsize == 16
 SEG_OK, SEG_EFRAMING, SEG_EOUTSIDE = 0, 1, 2  # PBFT_SEG_*
 
 
