@@ -311,6 +311,22 @@ int pbft_replica_reserve_streams(pbft_replica *r, uint64_t max_stream_bytes, uin
                                  uint32_t env_cap, uint32_t residue_cap);
 int pbft_replica_get_streams_stats(pbft_replica *r, pbft_replica_streams_stats *out);
 
+/* PrePrepares on the path of pbft_replica_push_streams.  The front half also brings one pbft_pp_head per residue entry
+ * (include/pbft_wire.h: pbft_verify_streams_admit_pp on the GPU context, pbft_wire_decode_preprepare under a verifier
+ * override).  A residue entry whose head is PBFT_PP_OK -- the canonical signed PrePrepare -- is then applied from the
+ * head: the signer and connection tests of pbft_replica_push_frames, counter for counter; the digest = the installed
+ * pbft_digest_fn on the operation's bytes where they lie in the caller's stream or, without an override, the head's
+ * `computed`; then what pbft_replica_on_pre_prepare does behind its digest.  No JSON parse, no pbft_digest_blake2b512
+ * call and no second context, so a replica with neither a digest override nor a GPU context ingests canonical
+ * PrePrepares.  Every other residue entry goes through the general parser as before, in frame order.
+ * on = 0: the heads are neither made nor used (the call as it was before the heads existed).  Default: 1. */
+int pbft_replica_set_streams_pp(pbft_replica *r, int on);
+typedef struct {
+  uint64_t from_head;   /* signed PrePrepare frames of the residue handled from a PBFT_PP_OK head          */
+  uint64_t from_parser; /* signed PrePrepare frames handled through pbft_wire_decode_json (any ingress)   */
+} pbft_replica_pp_stats;
+int pbft_replica_get_pp_stats(pbft_replica *r, pbft_replica_pp_stats *out);
+
 /* Non-blocking flush.  _submit: collect every READY sub-window (force = every pending candidate) into one
  * batch and launch it; *n_rows = its signatures (0: nothing launched); PBFT_EBUSY while a batch is in flight.
  * _poll: 1 once no batch is in flight -- the finished batch's accepted votes inserted, the events it

@@ -343,9 +343,65 @@ int pbft_verify_streams_admit(pbft_ctx *ctx, const uint8_t *stream, uint64_t str
                               uint64_t log_window, pbft_seg_head *seg_heads_out, uint32_t *n_frames_out,
                               uint32_t *counts_out, uint8_t *envelopes_out, uint32_t *n_env_out, uint64_t *present_out,
                               uint64_t *valid_out, pbft_admit_residue *res_out, uint32_t *n_res_out);
-/* Size the staging and the index, grouping, admission and verification workspaces of the call above for these caps. */
+/* Size the staging (the PrePrepare heads' residue_cap x sizeof(pbft_pp_head) included) and the index, grouping,
+ * admission and verification workspaces of the call above and of pbft_verify_streams_admit_pp for these caps. */
 int pbft_streams_admit_reserve(pbft_ctx *ctx, uint64_t max_stream_bytes, uint32_t max_segments, uint32_t n_replicas,
                                uint64_t frame_cap, uint32_t env_cap, uint32_t residue_cap, uint64_t log_window);
+
+/* ---- The residue's PrePrepares parsed and digested on the device (kernels: pbft_amd/csrc/wire_pp.hip; rule:
+ * wire_pp_core.h) ----
+ * The canonical signed PrePrepare, exactly what pbft_wire_encode_json writes,
+ *   {"PrePrepare":{"view":V,"sequence_number":N,"digest":"<128 hex>","message":{"operation":"OP","timestamp":T,
+ *   "client":"C"},"replica":R,"signature":"<128 hex>"}}
+ * with V, N, T serde u64, R <= 65535, lowercase hex, OP of 0 .. PBFT_PP_OP_MAX and C of 1 .. 63 bytes in 0x20 .. 0x7E
+ * other than '"' and '\', nothing behind "}}" (PBFT_PP_FRAME_MIN .. PBFT_PP_FRAME_MAX bytes), is PBFT_PP_OK.  Anything
+ * else -- a vote, a ClientRequest, whitespace, another field order, an escape, a non-ASCII or oversize operation -- is
+ * PBFT_PP_NONE: pbft_wire_decode_json decides.  PBFT_PP_OK implies that pbft_wire_decode_json accepts the frame as a
+ * PrePrepare with digest_ok and has_sig, the same view, seq, replica, timestamp, digest and signature, and an
+ * operation equal to bytes [op_off, op_off + op_len) of the body. */
+#define PBFT_PP_OP_MAX 3072
+#define PBFT_PP_FRAME_MIN 394
+#define PBFT_PP_FRAME_MAX (517 + PBFT_PP_OP_MAX)
+#define PBFT_PP_NONE 0
+#define PBFT_PP_OK 1
+typedef struct {
+  uint64_t view, seq, timestamp;
+  uint32_t op_off, op_len; /* the operation's bytes, counted from the body's first byte */
+  uint16_t replica;
+  uint8_t status; /* PBFT_PP_* */
+  uint8_t pad[5];
+  uint8_t claimed[64];  /* the frame's "digest" */
+  uint8_t computed[64]; /* Blake2b-512 of the operation */
+  uint8_t sig[64];
+} pbft_pp_head; /* all zero when status is PBFT_PP_NONE */
+
+/* Host, one frame, no context and no GPU: the rule above and the digest.  Returns 0 (the answer is out->status), or
+ * PBFT_EINVAL for a null argument. */
+int pbft_wire_decode_preprepare(const uint8_t *body, size_t len, pbft_pp_head *out);
+
+/* Device, enqueue only (two kernel nodes on one stream: no allocation, copy, memset or synchronisation, no lane waits
+ * for another block, every loop is bounded; capturable).  Entry i < min(d_n_res[0], residue_cap) of d_res (as
+ * pbft_admit_device wrote it; d_n_res NULL: all residue_cap entries are live) -> d_pp[i]; the entries behind that are
+ * zeroed.  d_stream as for pbft_wire_decode_frames_device: 16-byte aligned, readable up to stream_bytes rounded up to
+ * 16, only granules of that range are read; an entry that does not lie inside stream_bytes is PBFT_PP_NONE and is not
+ * read.  PBFT_EINVAL: a null or misaligned pointer (d_res, d_pp 8 bytes, d_n_res 4), stream_bytes > 2^31; a refused
+ * call has enqueued nothing.  residue_cap = 0 enqueues nothing. */
+int pbft_wire_decode_preprepares_device(pbft_ctx *ctx, const uint8_t *d_stream, uint64_t stream_bytes,
+                                        const pbft_admit_residue *d_res, const uint32_t *d_n_res, uint32_t residue_cap,
+                                        pbft_pp_head *d_pp, void *stream);
+
+/* pbft_verify_streams_admit with one more output, pp_out [residue_cap]; pp_out NULL is that call.  After the chain's one
+ * synchronisation, and only if counts_out[PBFT_ADMIT_HOST] is not 0, the two kernels above run over the
+ * k = min(n_res_out[0], residue_cap) residue entries where they lie on the device and pp_out[0 .. k) comes back: one
+ * more launch pair, copy and synchronisation.  Otherwise (no frame of the call can be a PrePrepare) pp_out is not
+ * touched and the call enqueues, copies and synchronises exactly as pbft_verify_streams_admit. */
+int pbft_verify_streams_admit_pp(pbft_ctx *ctx, const uint8_t *stream, uint64_t stream_bytes, const uint64_t *seg_off,
+                                 const uint64_t *seg_len, const uint16_t *seg_peer, uint32_t S, uint32_t n_replicas,
+                                 uint64_t frame_cap, uint32_t env_cap, uint32_t residue_cap, uint64_t view, uint64_t h,
+                                 uint64_t log_window, pbft_seg_head *seg_heads_out, uint32_t *n_frames_out,
+                                 uint32_t *counts_out, uint8_t *envelopes_out, uint32_t *n_env_out,
+                                 uint64_t *present_out, uint64_t *valid_out, pbft_admit_residue *res_out,
+                                 uint32_t *n_res_out, pbft_pp_head *pp_out);
 
 #ifdef __cplusplus
 }

@@ -67,6 +67,32 @@ pub struct pbft_admit_residue {
     pub frame: u32,
     pub len: u32,
 }
+/// One PrePrepare head of pbft_wire_decode_preprepares_device: 232 bytes, all zero unless status is PBFT_PP_OK.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct pbft_pp_head {
+    pub view: u64,
+    pub seq: u64,
+    pub timestamp: u64,
+    pub op_off: u32,
+    pub op_len: u32,
+    pub replica: u16,
+    pub status: u8,
+    pub pad: [u8; 5],
+    pub claimed: [u8; 64],
+    pub computed: [u8; 64],
+    pub sig: [u8; 64],
+}
+pub const PBFT_PP_NONE: u8 = 0;
+pub const PBFT_PP_OK: u8 = 1;
+pub const PBFT_PP_OP_MAX: u32 = 3072;
+/// Counters of the PrePrepares of pbft_replica_push_streams (pbft_replica_get_pp_stats).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct pbft_replica_pp_stats {
+    pub from_head: u64,
+    pub from_parser: u64,
+}
 pub const PBFT_ADMIT_CLEAN: u8 = 0;
 pub const PBFT_ADMIT_CONTESTED: u8 = 1;
 pub const PBFT_ADMIT_REJ_VIEW: u8 = 2;
@@ -453,4 +479,17 @@ extern "C" {
     pub fn pbft_replica_reserve_streams(r: *mut pbft_replica, max_stream_bytes: u64, max_segments: u32,
                                         frame_cap: u64, env_cap: u32, residue_cap: u32) -> c_int;
     pub fn pbft_replica_get_streams_stats(r: *mut pbft_replica, out: *mut pbft_replica_streams_stats) -> c_int;
+    pub fn pbft_wire_decode_preprepare(body: *const u8, len: usize, out: *mut pbft_pp_head) -> c_int;
+    pub fn pbft_wire_decode_preprepares_device(ctx: *mut pbft_ctx, d_stream: *const u8, stream_bytes: u64,
+                                               d_res: *const pbft_admit_residue, d_n_res: *const u32,
+                                               residue_cap: u32, d_pp: *mut pbft_pp_head, stream: *mut c_void) -> c_int;
+    pub fn pbft_verify_streams_admit_pp(ctx: *mut pbft_ctx, stream: *const u8, stream_bytes: u64, seg_off: *const u64,
+                                        seg_len: *const u64, seg_peer: *const u16, n_segments: u32, n_replicas: u32,
+                                        frame_cap: u64, env_cap: u32, residue_cap: u32, view: u64, h: u64,
+                                        log_window: u64, seg_heads_out: *mut pbft_seg_head, n_frames_out: *mut u32,
+                                        counts_out: *mut u32, envelopes_out: *mut u8, n_env_out: *mut u32,
+                                        present_out: *mut u64, valid_out: *mut u64, res_out: *mut pbft_admit_residue,
+                                        n_res_out: *mut u32, pp_out: *mut pbft_pp_head) -> c_int;
+    pub fn pbft_replica_set_streams_pp(r: *mut pbft_replica, on: c_int) -> c_int;
+    pub fn pbft_replica_get_pp_stats(r: *mut pbft_replica, out: *mut pbft_replica_pp_stats) -> c_int;
 }

@@ -613,6 +613,15 @@ pub fn key_from_peer_id(peer_id: &[u8]) -> Result<[u8; 32]> {
     Ok(a)
 }
 
+/// One frame body against the canonical signed-PrePrepare rule, on the host (pbft_wire_decode_preprepare): `Some(head)`
+/// with the fields, where the operation lies in `body` and its Blake2b-512, or `None`: the general parser decides.
+pub fn decode_preprepare(body: &[u8]) -> Result<Option<ffi::pbft_pp_head>> {
+    let mut h = std::mem::MaybeUninit::<ffi::pbft_pp_head>::zeroed();
+    check(unsafe { ffi::pbft_wire_decode_preprepare(body.as_ptr(), body.len(), h.as_mut_ptr()) })?;
+    let h = unsafe { h.assume_init() };
+    Ok(if h.status == ffi::PBFT_PP_OK { Some(h) } else { None })
+}
+
 /// Round events reported by [`Replica::flush`].
 #[derive(Clone, Copy, Debug, PartialEq, Eq)]
 pub enum RoundEvent {
@@ -824,6 +833,16 @@ impl<'a> Replica<'a> {
     pub fn streams_stats(&self) -> ffi::pbft_replica_streams_stats {
         let mut s = ffi::pbft_replica_streams_stats::default();
         unsafe { ffi::pbft_replica_get_streams_stats(self.raw, &mut s) };
+        s
+    }
+    /// Whether `push_streams` applies the residue's canonical PrePrepares from the heads the front half brings
+    /// (pbft_replica_set_streams_pp; default on).  Off: every PrePrepare goes through the general parser.
+    pub fn set_streams_pp(&mut self, on: bool) -> Result<()> {
+        check(unsafe { ffi::pbft_replica_set_streams_pp(self.raw, on as c_int) }).map(|_| ())
+    }
+    pub fn pp_stats(&self) -> ffi::pbft_replica_pp_stats {
+        let mut s = ffi::pbft_replica_pp_stats::default();
+        unsafe { ffi::pbft_replica_get_pp_stats(self.raw, &mut s) };
         s
     }
     /// 160-byte binary records (pbft_wire.h PBFT_RECORD_BYTES) read from peer `peer_idx`'s connection;

@@ -30,7 +30,8 @@ EXPORTS = (
     "pbft_verify_frames_device", "pbft_verify_frames", "pbft_verify_frames_tally_device", "pbft_verify_frames_tally",
     "pbft_wire_index_streams_device", "pbft_index_reserve", "pbft_verify_streams_tally_device",
     "pbft_verify_streams_tally", "pbft_admit_device", "pbft_admit_reserve", "pbft_verify_streams_admit",
-    "pbft_streams_admit_reserve",
+    "pbft_streams_admit_reserve", "pbft_wire_decode_preprepare", "pbft_wire_decode_preprepares_device",
+    "pbft_verify_streams_admit_pp",
 )
 
 ERRORS = {0: "PBFT_OK", -1: "PBFT_EINVAL", -2: "PBFT_EHIP", -3: "PBFT_ENOKEYS",
@@ -141,6 +142,10 @@ def load() -> ctypes.CDLL:
         "pbft_verify_streams_admit": (i32, [vp, vp, u64, vp, vp, vp, u32, u32, u64, u32, u32, u64, u64, u64, vp, vp, vp,
                                             vp, vp, vp, vp, vp, vp]),
         "pbft_streams_admit_reserve": (i32, [vp, u64, u32, u32, u64, u32, u32, u64]),
+        "pbft_wire_decode_preprepare": (i32, [vp, ctypes.c_size_t, vp]),
+        "pbft_wire_decode_preprepares_device": (i32, [vp, vp, u64, vp, vp, u32, vp, vp]),
+        "pbft_verify_streams_admit_pp": (i32, [vp, vp, u64, vp, vp, vp, u32, u32, u64, u32, u32, u64, u64, u64, vp, vp,
+                                               vp, vp, vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

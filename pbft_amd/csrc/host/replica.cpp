@@ -52,6 +52,10 @@
 // replica without a verifier override reports PBFT_ENODEV.
 #pragma weak pbft_verify_streams_admit
 #pragma weak pbft_streams_admit_reserve
+// So are the PrePrepare heads (wire_pp.hip, which is compiled with the kernels): without them every PrePrepare of
+// pbft_replica_push_streams takes the general parser, as with pbft_replica_set_streams_pp(r, 0).
+#pragma weak pbft_verify_streams_admit_pp
+#pragma weak pbft_wire_decode_preprepare
 
 namespace {
 
@@ -245,6 +249,8 @@ struct StreamsFront {
   std::vector<uint8_t> envelopes;        // [env_cap][85]
   std::vector<uint64_t> present, valid;  // [env_cap][W]
   std::vector<pbft_admit_residue> res;   // [residue_cap]
+  std::vector<pbft_pp_head> pp;          // [residue_cap]: the residue's PrePrepare heads, valid only if pp_live
+  bool pp_live = false;
 };
 
 // Worker threads for the batch fill and the bitmap application: one pool per process, started on first use and
@@ -528,6 +534,8 @@ struct pbft_replica {
   bool defer_eval = false;       // the batch in flight shares windows with `pend`: they are evaluated once, after both
   StreamsFront front;
   pbft_replica_streams_stats sstats{};
+  bool streams_pp = true;  // pbft_replica_set_streams_pp
+  pbft_replica_pp_stats ppstats{};
 };
 
 static uint32_t primary_of(const pbft_replica* r, uint64_t view) { return (uint32_t)(view % r->n); }
@@ -1620,6 +1628,9 @@ int pbft_replica_set_log_window(pbft_replica* r, uint64_t log_window) {
   return PBFT_OK;
 }
 
+static int pre_prepare_apply(pbft_replica* r, uint64_t view, uint64_t seq, const uint8_t* d,
+                             const uint8_t* claimed_digest, const uint8_t* primary_sig);
+
 // validate_pre_prepare (src/behavior.rs:126-157) + State::insert_pre_prepare (src/state.rs:40-47);
 // the signature (TODO :127) is checked by the next flush, batched with the votes.  peer_idx is the
 // authenticated sender (inject_node_event's peer_id, src/behavior.rs:304, arm :310-318): only the view's
@@ -1652,6 +1663,13 @@ int pbft_replica_on_pre_prepare(pbft_replica* r, uint32_t peer_idx, uint64_t vie
   }
   if (rc) return rc;
   if (digest_out) memcpy(digest_out, d, 64);
+  return pre_prepare_apply(r, view, seq, d, claimed_digest, primary_sig);
+}
+
+// A PrePrepare from the view's primary on its own connection whose operation hashes to d: everything behind the
+// digest.  Also the end of the head path of pbft_replica_push_streams, which brings d from the device.
+static int pre_prepare_apply(pbft_replica* r, uint64_t view, uint64_t seq, const uint8_t* d,
+                             const uint8_t* claimed_digest, const uint8_t* primary_sig) {
   ++r->stats.pushed;
   if (memcmp(d, claimed_digest, 64) != 0) { ++r->stats.rejected_digest; return 0; }  // validate_digest :139-145
   if (view != r->current_view) { ++r->stats.rejected_view; return 0; }                // :134-141
@@ -2635,6 +2653,7 @@ static int push_frame_body(pbft_replica* r, uint32_t peer_idx, const char* js, s
     // only on the primary's own connection (the reference receives it from the primary, src/behavior.rs:89-95):
     // a relayed PrePrepare could otherwise fill the window's candidate slots ahead of the real one
     const uint32_t p = r->n ? primary_of(r, m.view) : 0;
+    ++r->ppstats.from_parser;
     if (r->n == 0 || m.replica != p) { ++r->stats.rejected_signer; return 0; }
     // (on_pre_prepare rejects a connection that is not the primary's)
     return pbft_replica_on_pre_prepare(r, peer_idx, m.view, m.seq, (const uint8_t*)m.operation, m.operation_len,
@@ -2799,6 +2818,12 @@ static int streams_front_host(pbft_replica* r, const uint8_t* stream, const uint
   }
   F.n_res[0] = (uint32_t)F.res.size();
   F.n_res[1] = 0;
+  F.pp_live = r->streams_pp && pbft_wire_decode_preprepare && F.counts[pbft::ADMIT_HOST];
+  if (F.pp_live) {  // the heads the device would bring, by the host build of the same rule
+    F.pp.resize(F.res.size());
+    for (size_t i = 0; i < F.res.size(); ++i)
+      pbft_wire_decode_preprepare(stream + F.res[i].off, F.res[i].len, &F.pp[i]);
+  }
   // group the clean rows by envelope, verify them through the override, fold the two sets
   const uint64_t C = clean_rows.size();
   std::map<std::string, uint32_t> env_of;
@@ -2862,6 +2887,7 @@ static bool streams_residue_conflict(pbft_replica* r, const uint8_t* stream, uin
     const pbft_admit_residue& e = F.res[i];
     while (s < S && e.frame >= F.seg[s].first + F.seg[s].n_frames) ++s;
     if (s >= S || e.off > stream_bytes || e.len > stream_bytes - e.off) return true;  // (the host sequence decides)
+    if (F.pp_live && F.pp[i].status == PBFT_PP_OK) continue;  // a PrePrepare: not a vote
     pbft_wire_msg m;
     if (pbft_wire_decode_json((const char*)stream + e.off, e.len, &m, arena, sizeof arena) != 0 || !m.digest_ok ||
         !m.has_sig || (m.kind != PBFT_MSG_PREPARE && m.kind != PBFT_MSG_COMMIT) || m.replica != seg_peer[s] ||
@@ -2882,6 +2908,18 @@ static int streams_front_device(pbft_replica* r, const uint8_t* stream, uint64_t
   F.present.resize((size_t)F.env_cap * F.W);
   F.valid.resize((size_t)F.env_cap * F.W);
   F.res.resize(F.residue_cap);
+  F.pp_live = false;
+  if (r->streams_pp && pbft_verify_streams_admit_pp) {
+    F.pp.resize(F.residue_cap);
+    const int rc = pbft_verify_streams_admit_pp(r->ctx, stream, stream_bytes, seg_off, seg_len, seg_peer, S, r->n,
+                                                F.frame_cap, F.env_cap, F.residue_cap, r->current_view, r->h,
+                                                r->log_window, F.seg.data(), F.n_frames, F.counts, F.envelopes.data(),
+                                                F.n_env, F.present.data(), F.valid.data(), F.res.data(), F.n_res,
+                                                F.pp.data());
+    // (the heads were written only if a frame was deferred to the host, and only those of the residue within the cap)
+    F.pp_live = rc == PBFT_OK && F.counts[pbft::ADMIT_HOST] != 0 && F.n_res[0] <= F.residue_cap;
+    return rc;
+  }
   if (!pbft_verify_streams_admit) return PBFT_ENODEV;
   return pbft_verify_streams_admit(r->ctx, stream, stream_bytes, seg_off, seg_len, seg_peer, S, r->n, F.frame_cap,
                                    F.env_cap, F.residue_cap, r->current_view, r->h, r->log_window, F.seg.data(),
@@ -2949,7 +2987,29 @@ int pbft_replica_push_streams(pbft_replica* r, const uint8_t* stream, uint64_t s
       const pbft_admit_residue& e = F.res[i];
       while (s < S && e.frame >= F.seg[s].first + F.seg[s].n_frames) ++s;
       if (s >= S || e.off > stream_bytes || e.len > stream_bytes - e.off) { rc = PBFT_EINVAL; break; }
-      const int got = push_frame_body(r, seg_peer[s], (const char*)stream + e.off, e.len);
+      int got;
+      if (F.pp_live && F.pp[i].status == PBFT_PP_OK) {
+        // a canonical PrePrepare, parsed and hashed by the front half: push_frame_body -> on_pre_prepare, counter
+        // for counter, without the parse and without the digest call
+        const pbft_pp_head& hd = F.pp[i];
+        const uint32_t prim = r->n ? primary_of(r, hd.view) : 0;
+        ++r->ppstats.from_head;
+        got = 0;
+        if (r->n == 0 || hd.replica != prim) {
+          ++r->stats.rejected_signer;
+        } else if (seg_peer[s] != prim) {
+          ++r->stats.pushed;
+          ++r->stats.rejected_signer;
+        } else if (r->digest_fn) {
+          uint8_t d[64];
+          got = r->digest_fn(r->digest_user, stream + e.off + hd.op_off, hd.op_len, d);
+          if (got == 0) got = pre_prepare_apply(r, hd.view, hd.seq, d, hd.claimed, hd.sig);
+        } else {
+          got = pre_prepare_apply(r, hd.view, hd.seq, hd.computed, hd.claimed, hd.sig);
+        }
+      } else {
+        got = push_frame_body(r, seg_peer[s], (const char*)stream + e.off, e.len);
+      }
       if (got < 0) rc = got;
       else if (got == 1) ++*pushed;
       else ++*dropped;
@@ -3024,6 +3084,18 @@ int pbft_replica_reserve_streams(pbft_replica* r, uint64_t max_stream_bytes, uin
   if (!pbft_streams_admit_reserve) return PBFT_ENODEV;
   return pbft_streams_admit_reserve(r->ctx, max_stream_bytes, max_segments, r->n, frame_cap, env_cap, residue_cap,
                                     r->log_window);
+}
+
+int pbft_replica_set_streams_pp(pbft_replica* r, int on) {
+  if (!r) return PBFT_EINVAL;
+  r->streams_pp = on != 0;
+  return PBFT_OK;
+}
+
+int pbft_replica_get_pp_stats(pbft_replica* r, pbft_replica_pp_stats* out) {
+  if (!r || !out) return PBFT_EINVAL;
+  *out = r->ppstats;
+  return PBFT_OK;
 }
 
 int pbft_replica_get_streams_stats(pbft_replica* r, pbft_replica_streams_stats* out) {

@@ -39,6 +39,7 @@ using namespace pbft;
 #include "group_kernels.h"
 #include "wire_decode_kernels.h"
 #include "wire_index_kernels.h"
+#include "wire_pp_kernels.h"
 // Finish configuration by batch size (signatures per lane, product tree, waves per SIMD), measured on MI355X
 // with the lane-parallel wave inversion (profiles/r03/ab_finish.txt): 131k 0.2115 -> 0.1906 ms (width 2),
 // 262k 0.3628 -> 0.3429 (width 4), 2^20 finish kernel 118.6 -> 91.4 us (width 8, tree, 2 waves per SIMD).
@@ -2625,7 +2626,7 @@ struct admit_layout {
   frames_layout lay;
   uint32_t W;
   size_t env_bytes, set_bytes, o_soff, o_slen, o_shead, o_nfr, o_speer, o_idx, o_env, o_n, o_present, o_valid, o_cnt,
-      o_cls, o_counts, o_clean, o_res, o_nres, total;
+      o_cls, o_counts, o_clean, o_res, o_nres, o_pp, total;
   admit_layout(uint64_t stream_bytes, uint32_t S, uint64_t frame_cap, uint32_t env_cap, uint32_t residue_cap,
                uint32_t n_replicas)
       : lay(frame_cap, stream_bytes) {
@@ -2649,7 +2650,8 @@ struct admit_layout {
     o_clean = o_counts + 32;
     o_res = o_clean + up(8 * (((size_t)frame_cap + 63) / 64));
     o_nres = o_res + sizeof(pbft_admit_residue) * (size_t)residue_cap;
-    total = o_nres + 16 + 256;
+    o_pp = o_nres + 16;  // (8-byte aligned: the PrePrepare heads of pbft_verify_streams_admit_pp)
+    total = o_pp + sizeof(pbft_pp_head) * (size_t)residue_cap + 256;
   }
 };
 
@@ -2678,12 +2680,26 @@ int pbft_streams_admit_reserve(pbft_ctx* c, uint64_t max_stream_bytes, uint32_t 
   return ensure_work(c, frame_cap, true);
 }
 
-int pbft_verify_streams_admit(pbft_ctx* c, const uint8_t* stream, uint64_t stream_bytes, const uint64_t* seg_off,
-                              const uint64_t* seg_len, const uint16_t* seg_peer, uint32_t S, uint32_t n_replicas,
-                              uint64_t frame_cap, uint32_t env_cap, uint32_t residue_cap, uint64_t view, uint64_t h,
-                              uint64_t log_window, pbft_seg_head* seg_heads_out, uint32_t* n_frames_out,
-                              uint32_t* counts_out, uint8_t* envelopes_out, uint32_t* n_env_out, uint64_t* present_out,
-                              uint64_t* valid_out, pbft_admit_residue* res_out, uint32_t* n_res_out) {
+int pbft_wire_decode_preprepares_device(pbft_ctx* c, const uint8_t* d_stream, uint64_t stream_bytes,
+                                        const pbft_admit_residue* d_res, const uint32_t* d_n_res, uint32_t residue_cap,
+                                        pbft_pp_head* d_pp, void* stream) {
+  if (!c) return set_err(PBFT_EINVAL, "null context");
+  if (!d_res || !d_pp || (stream_bytes && !d_stream)) return set_err(PBFT_EINVAL, "null PrePrepare argument");
+  if (((uintptr_t)d_stream & 15) || ((uintptr_t)d_res & 7) || ((uintptr_t)d_pp & 7) || ((uintptr_t)d_n_res & 3))
+    return set_err(PBFT_EINVAL, "misaligned PrePrepare pointer");
+  if (stream_bytes > pbft::IX_MAX_STREAM) return set_err(PBFT_EINVAL, "more than 2^31 stream bytes");
+  if (residue_cap == 0) return PBFT_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(launch_pp(d_stream, stream_bytes, d_res, d_n_res, residue_cap, d_pp, stream ? (hipStream_t)stream : c->stream));
+  return PBFT_OK;
+}
+
+static int streams_admit(pbft_ctx* c, const uint8_t* stream, uint64_t stream_bytes, const uint64_t* seg_off,
+                         const uint64_t* seg_len, const uint16_t* seg_peer, uint32_t S, uint32_t n_replicas,
+                         uint64_t frame_cap, uint32_t env_cap, uint32_t residue_cap, uint64_t view, uint64_t h,
+                         uint64_t log_window, pbft_seg_head* seg_heads_out, uint32_t* n_frames_out,
+                         uint32_t* counts_out, uint8_t* envelopes_out, uint32_t* n_env_out, uint64_t* present_out,
+                         uint64_t* valid_out, pbft_admit_residue* res_out, uint32_t* n_res_out, pbft_pp_head* pp_out) {
   int rc = check_streams_admit_shape(c, stream_bytes, S, n_replicas, frame_cap, env_cap, log_window);
   if (rc) return rc;
   if (c->in_flight) return set_err(PBFT_EBUSY, "async batch in flight");
@@ -2747,7 +2763,38 @@ int pbft_verify_streams_admit(pbft_ctx* c, const uint8_t* stream, uint64_t strea
                            hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(n_res_out, d + L.o_nres, 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
+  // The PrePrepares of the residue, where it lies: only now is it known whether there can be one, and how many entries
+  // there are.  A call without a deferred frame ends here, as it always did.
+  const uint32_t k = n_res_out[0] < residue_cap ? n_res_out[0] : residue_cap;
+  if (pp_out && counts_out[PBFT_ADMIT_HOST] && k) {
+    HIP_TRY(launch_pp(d + L.lay.stream, stream_bytes, d + L.o_res, nullptr, k, d + L.o_pp, st));
+    HIP_TRY(hipMemcpyAsync(pp_out, d + L.o_pp, sizeof(pbft_pp_head) * (size_t)k, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+  }
   return PBFT_OK;
+}
+
+int pbft_verify_streams_admit(pbft_ctx* c, const uint8_t* stream, uint64_t stream_bytes, const uint64_t* seg_off,
+                              const uint64_t* seg_len, const uint16_t* seg_peer, uint32_t S, uint32_t n_replicas,
+                              uint64_t frame_cap, uint32_t env_cap, uint32_t residue_cap, uint64_t view, uint64_t h,
+                              uint64_t log_window, pbft_seg_head* seg_heads_out, uint32_t* n_frames_out,
+                              uint32_t* counts_out, uint8_t* envelopes_out, uint32_t* n_env_out, uint64_t* present_out,
+                              uint64_t* valid_out, pbft_admit_residue* res_out, uint32_t* n_res_out) {
+  return streams_admit(c, stream, stream_bytes, seg_off, seg_len, seg_peer, S, n_replicas, frame_cap, env_cap,
+                       residue_cap, view, h, log_window, seg_heads_out, n_frames_out, counts_out, envelopes_out,
+                       n_env_out, present_out, valid_out, res_out, n_res_out, nullptr);
+}
+
+int pbft_verify_streams_admit_pp(pbft_ctx* c, const uint8_t* stream, uint64_t stream_bytes, const uint64_t* seg_off,
+                                 const uint64_t* seg_len, const uint16_t* seg_peer, uint32_t S, uint32_t n_replicas,
+                                 uint64_t frame_cap, uint32_t env_cap, uint32_t residue_cap, uint64_t view, uint64_t h,
+                                 uint64_t log_window, pbft_seg_head* seg_heads_out, uint32_t* n_frames_out,
+                                 uint32_t* counts_out, uint8_t* envelopes_out, uint32_t* n_env_out,
+                                 uint64_t* present_out, uint64_t* valid_out, pbft_admit_residue* res_out,
+                                 uint32_t* n_res_out, pbft_pp_head* pp_out) {
+  return streams_admit(c, stream, stream_bytes, seg_off, seg_len, seg_peer, S, n_replicas, frame_cap, env_cap,
+                       residue_cap, view, h, log_window, seg_heads_out, n_frames_out, counts_out, envelopes_out,
+                       n_env_out, present_out, valid_out, res_out, n_res_out, pp_out);
 }
 
 static int run_digest(pbft_ctx* c, int kind, const uint8_t* data, const uint64_t* offsets, const uint32_t* lens,

@@ -40,7 +40,9 @@ struct frame_fields {
 template <class Rd>
 struct frame_cursor {
   const Rd& rd;
-  uint32_t p, e;  // next byte and end of the frame, as byte positions in the row (e <= 382)
+  // next byte and end of the frame, as byte positions in the row (e <= 382 for a vote's row; any row works whose
+  // accessor serves the dword behind the one that holds byte e - 1: wire_pp_core.h's rows are longer)
+  uint32_t p, e;
 
   // the 4 bytes at row position at (at < e), little endian; the upper ones may lie past the frame
   __host__ __device__ uint32_t word4(uint32_t at) const {

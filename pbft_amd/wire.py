@@ -31,6 +31,14 @@ assert SegHead.itemsize == 24
 AdmitResidue = np.dtype([("off", "<u8"), ("frame", "<u4"), ("len", "<u4")])
 assert AdmitResidue.itemsize == 16
 SEG_OK, SEG_EFRAMING, SEG_EOUTSIDE = 0, 1, 2  # PBFT_SEG_*
+# pbft_pp_head (include/pbft_wire.h): one per residue entry of decode_preprepares_device / verify_streams_admit_pp
+PpHead = np.dtype([("view", "<u8"), ("seq", "<u8"), ("timestamp", "<u8"), ("op_off", "<u4"), ("op_len", "<u4"),
+                   ("replica", "<u2"), ("status", "u1"), ("pad", "u1", 5), ("claimed", "u1", 64),
+                   ("computed", "u1", 64), ("sig", "u1", 64)])
+assert PpHead.itemsize == 232
+PP_NONE, PP_OK = 0, 1  # PBFT_PP_*
+PP_OP_MAX = 3072
+PP_FRAME_MIN, PP_FRAME_MAX = 394, 517 + PP_OP_MAX  # byte lengths of a canonical signed PrePrepare
 
 
 class _Msg(ctypes.Structure):
@@ -118,6 +126,15 @@ def decode_json(js: bytes) -> WireMsg:
     return WireMsg(kind=cm.kind, view=cm.view, seq=cm.seq, digest=bytes(cm.digest),
                    replica=cm.replica if cm.has_sig else None, sig=bytes(cm.sig) if cm.has_sig else None,
                    operation=op, timestamp=cm.timestamp, client=cm.client.decode(), digest_ok=bool(cm.digest_ok))
+
+
+def decode_preprepare(body: bytes) -> np.ndarray:
+    """pbft_wire_decode_preprepare: the canonical-PrePrepare rule and the operation's digest for one frame body, on the
+    host.  Returns one PpHead record (status PP_OK, or all zero: the general parser decides)."""
+    out = np.zeros(1, PpHead)
+    src = ctypes.create_string_buffer(bytes(body), max(1, len(body)))
+    check(load().pbft_wire_decode_preprepare(src, len(body), out.ctypes.data))
+    return out[0]
 
 
 @dataclass
