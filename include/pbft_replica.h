@@ -327,6 +327,46 @@ typedef struct {
 } pbft_replica_pp_stats;
 int pbft_replica_get_pp_stats(pbft_replica *r, pbft_replica_pp_stats *out);
 
+/* ---- egress: the replica's own votes ----
+ * A PBFT_EVENT_PRE_PREPARED obliges the replica to multicast its signed Prepare and a PBFT_EVENT_PREPARED its signed
+ * Commit (src/behavior.rs:105-122, :349-362).  While the outbox is on, every such event also appends the vote's
+ * envelope -- kind 1 for PRE_PREPARED, kind 2 for PREPARED, with the window's digest as it is when the event is
+ * decided -- to the outbox, in event order (a window that is prepared, committed and garbage-collected in one flush
+ * still leaves its Commit there).  With the outbox off (the default) nothing changes anywhere.
+ *
+ * pbft_replica_set_signing_seed: the replica signs on the GPU.  The seed is installed (pbft_sign_set_seed) on the
+ * replica's own clone of its context (ctxs[0]'s for pbft_replica_create_multi; created here if it does not exist yet),
+ * so emitting never waits for, or collides with, the votes batch in flight.  PBFT_EINVAL, with nothing changed, unless
+ * the seed's public key is keys[self_id] (or without a GPU context).  Turns the outbox on.  seed = NULL: the seed is
+ * cleared, and without a signer override the outbox is turned off and emptied.
+ * pbft_replica_set_signer: an override that signs and encodes, for replicas and tests without a GPU: fn receives the N
+ * queued envelopes (stride 85) and this replica's index, and writes the N frames to out (cap bytes), *len = their
+ * bytes, sigs[N][64] = R || S of each; it returns 0 or a negative code.  It takes precedence over the seed.  Installing
+ * one turns the outbox on; fn = NULL removes it (the outbox then stays on only if a seed is installed). */
+typedef int (*pbft_signer_fn)(void *user, const uint8_t *envelopes, uint64_t N, uint32_t replica, uint8_t *out,
+                              size_t cap, size_t *len, uint8_t *sigs);
+int pbft_replica_set_signing_seed(pbft_replica *r, const uint8_t *seed /* 32, NULL clears */);
+int pbft_replica_set_signer(pbft_replica *r, pbft_signer_fn fn, void *user);
+/* Sign and encode the whole outbox in one call: out receives the votes' frames in event order (what the caller writes
+ * to every connected peer), *len their bytes, *n_votes their number (both optional outputs are 0 unless votes were
+ * emitted, except *len below); the outbox is drained on success.  The length is known before anything is signed: if
+ * cap is smaller, PBFT_EINVAL, *len = the exact length needed and the outbox stays as it was; out = NULL with
+ * cap = 0 is the size query (returns 0).  An empty outbox, or one that is off: 0 votes.
+ * PBFT_EMIT_LOOPBACK: every emitted vote is also pushed as this replica's own, exactly as pbft_replica_push(kind,
+ * view, seq, digest, signer = self_id, sig) would -- verified in the next flush like anyone's (the reference's
+ * insert_prepare / insert_commit of its own vote, src/behavior.rs:107-110). */
+#define PBFT_EMIT_LOOPBACK 1u
+int pbft_replica_emit_frames(pbft_replica *r, uint32_t flags, uint8_t *out, size_t cap, size_t *len,
+                             uint64_t *n_votes);
+typedef struct {
+  uint64_t queued;          /* votes in the outbox now                                 */
+  uint64_t emitted;         /* votes signed and encoded by pbft_replica_emit_frames    */
+  uint64_t calls;           /* pbft_replica_emit_frames calls that emitted votes       */
+  uint64_t loopback_pushed; /* own votes queued by PBFT_EMIT_LOOPBACK                  */
+  uint64_t emit_ns;         /* host time inside those calls                            */
+} pbft_replica_egress_stats;
+int pbft_replica_get_egress_stats(pbft_replica *r, pbft_replica_egress_stats *out);
+
 /* Non-blocking flush.  _submit: collect every READY sub-window (force = every pending candidate) into one
  * batch and launch it; *n_rows = its signatures (0: nothing launched); PBFT_EBUSY while a batch is in flight.
  * _poll: 1 once no batch is in flight -- the finished batch's accepted votes inserted, the events it

@@ -374,6 +374,16 @@ int pbft_sign_batch(pbft_ctx *ctx, const uint8_t *seeds, uint32_t n_seeds, const
                     const uint8_t *msg, uint32_t msg_len, uint32_t msg_stride, uint64_t N, uint8_t *R,
                     uint8_t *S, uint8_t *pub);
 
+/* The context's own signing identity, for the frames forms of include/pbft_wire.h (pbft_sign_votes_frames*): the
+ * seed is expanded once, by a one-lane kernel -- SHA-512(seed) -> the clamped scalar a and the prefix, A = [a]B --
+ * and the 96 bytes a || prefix || A stay in a device buffer of the context with the replica index (<= 65535) that the
+ * frames carry; the seed's device staging is zeroed by that kernel.  pub_out (optional, 32 bytes) receives A.
+ * seed = NULL clears the state (the buffer is zeroed).  Blocking; PBFT_EBUSY while an async batch is in flight.
+ * A clone (pbft_verify_ctx_clone) does not inherit the seed.  The signing kernels index their tables by secret
+ * digits, as pbft_sign_batch's do: not constant-time against a co-tenant of the GPU. */
+int pbft_sign_set_seed(pbft_ctx *ctx, const uint8_t *seed /* 32, NULL clears */, uint32_t replica,
+                       uint8_t *pub_out /* 32, optional */);
+
 /* Tuning options of one context (defaults are chosen by batch size / free HBM):
  *   PBFT_OPT_SPLIT_BELOW          batches below this many signatures use the 4-lanes-per-signature latency
  *                                 kernel (default 12288; env PBFT_SPLIT_BELOW)
@@ -430,6 +440,7 @@ int pbft_sign_batch(pbft_ctx *ctx, const uint8_t *seeds, uint32_t n_seeds, const
  * default, 16384; 0 restores the default; anything else is PBFT_EINVAL.  The output does not depend on it; the
  * workspace does, so set it before pbft_index_reserve. */
 #define PBFT_OPT_INDEX_TILE 19
+/* (20, 21: PBFT_OPT_EGRESS_BLOCK / _DIRECT, with the egress forms they tune in include/pbft_wire.h) */
 int pbft_verify_set_option(pbft_ctx *ctx, int option, uint64_t value);
 
 /* Diagnostics */

@@ -403,6 +403,39 @@ int pbft_verify_streams_admit_pp(pbft_ctx *ctx, const uint8_t *stream, uint64_t 
                                  uint64_t *present_out, uint64_t *valid_out, pbft_admit_residue *res_out,
                                  uint32_t *n_res_out, pbft_pp_head *pp_out);
 
+/* ---- egress: the replica's own votes signed and framed on the device (kernels: pbft_amd/csrc/egress.hip) ----
+ * The other direction of everything above.  Envelope i = the 85 bytes at env + i * env_stride (env_stride >= 85,
+ * pbft_envelope: "PBFT" | kind | view LE | seq LE | digest[64]) is both the signed message and everything its frame
+ * holds except the signer.  The context signs it with the identity of pbft_sign_set_seed (include/pbft_verify.h;
+ * PBFT_EINVAL without one) and writes the canonical frame of that vote, with "replica" = the index given there.  The
+ * output is the concatenation of the N frames, byte for byte what pbft_wire_encode_votes writes for the same votes with
+ * RFC 8032 signatures (which are deterministic): frame i occupies [frame_off[i], frame_off[i + 1]) and frame_off[N] is
+ * the total.  An envelope whose magic is wrong or whose kind is not 1 (Prepare) or 2 (Commit) has no frame: length 0,
+ * signature 64 zero bytes; its neighbours are unaffected.  sigs (optional) receives R || S of every envelope.
+ *
+ * Device form, enqueue only on `stream` (NULL = the context's): three kernel nodes -- the frame lengths and their scan
+ * inside each 64-envelope tile, the scan over the tiles, one signature per lane and the frames -- with no allocation,
+ * copy, memset or synchronisation once pbft_egress_reserve(max_n >= N) has sized the workspace (8 bytes per 64
+ * envelopes); capturable as a plain chain.  N <= 2^24.  d_out may have any alignment; d_frame_off [N + 1] is 8-byte
+ * aligned, d_sigs [N][64] 4-byte.  Nothing is read beyond envelope N - 1's 85 bytes.  When the stream would exceed
+ * out_cap, the frames that do not fit entirely are not written, none is written in part, nothing at or beyond
+ * d_out + out_cap is touched, and d_frame_off (and d_sigs) are still complete.  Calls of one context share the
+ * workspace and must be ordered, like its verify launches. */
+/* Measuring (pbft_verify_set_option): the form of the signing kernel: lanes per workgroup, 64 (default; 0 restores
+ * it) or 256, and 1 = every lane stores its own frame bytewise instead of the wave staging its 64 frames in LDS and
+ * storing the span with 16-byte stores (default 0).  The output does not depend on either. */
+#define PBFT_OPT_EGRESS_BLOCK 20
+#define PBFT_OPT_EGRESS_DIRECT 21
+int pbft_egress_reserve(pbft_ctx *ctx, uint64_t max_n);
+int pbft_sign_votes_frames_device(pbft_ctx *ctx, const uint8_t *d_env, uint32_t env_stride, uint64_t N,
+                                  uint8_t *d_out, uint64_t out_cap, uint64_t *d_frame_off, uint8_t *d_sigs,
+                                  void *stream);
+/* Blocking, host buffers.  *len = the bytes needed, computed on the host before anything runs; when cap is smaller:
+ * PBFT_EINVAL, nothing written and nothing launched (out = NULL, cap = 0 asks for the length).  frame_off [N + 1]
+ * and sigs [N][64] are optional.  PBFT_EBUSY while an async batch is in flight on the context. */
+int pbft_sign_votes_frames(pbft_ctx *ctx, const uint8_t *envelopes, uint32_t env_stride, uint64_t N, uint8_t *out,
+                           size_t cap, size_t *len, uint64_t *frame_off, uint8_t *sigs);
+
 #ifdef __cplusplus
 }
 #endif

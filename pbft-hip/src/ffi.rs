@@ -93,6 +93,21 @@ pub struct pbft_replica_pp_stats {
     pub from_head: u64,
     pub from_parser: u64,
 }
+/// Counters of the replica's egress (pbft_replica_get_egress_stats).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct pbft_replica_egress_stats {
+    pub queued: u64,
+    pub emitted: u64,
+    pub calls: u64,
+    pub loopback_pushed: u64,
+    pub emit_ns: u64,
+}
+pub const PBFT_EMIT_LOOPBACK: u32 = 1;
+/// Signer override of pbft_replica_set_signer: (user, envelopes, N, replica, out, cap, len, sigs).
+pub type pbft_signer_fn = Option<unsafe extern "C" fn(user: *mut c_void, envelopes: *const u8, n: u64, replica: u32,
+                                                       out: *mut u8, cap: usize, len: *mut usize, sigs: *mut u8)
+                                                       -> c_int>;
 pub const PBFT_ADMIT_CLEAN: u8 = 0;
 pub const PBFT_ADMIT_CONTESTED: u8 = 1;
 pub const PBFT_ADMIT_REJ_VIEW: u8 = 2;
@@ -492,4 +507,16 @@ extern "C" {
                                         n_res_out: *mut u32, pp_out: *mut pbft_pp_head) -> c_int;
     pub fn pbft_replica_set_streams_pp(r: *mut pbft_replica, on: c_int) -> c_int;
     pub fn pbft_replica_get_pp_stats(r: *mut pbft_replica, out: *mut pbft_replica_pp_stats) -> c_int;
+    pub fn pbft_sign_set_seed(ctx: *mut pbft_ctx, seed: *const u8, replica: u32, pub_out: *mut u8) -> c_int;
+    pub fn pbft_egress_reserve(ctx: *mut pbft_ctx, max_n: u64) -> c_int;
+    pub fn pbft_sign_votes_frames_device(ctx: *mut pbft_ctx, d_env: *const u8, env_stride: u32, n: u64,
+                                         d_out: *mut u8, out_cap: u64, d_frame_off: *mut u64, d_sigs: *mut u8,
+                                         stream: *mut c_void) -> c_int;
+    pub fn pbft_sign_votes_frames(ctx: *mut pbft_ctx, envelopes: *const u8, env_stride: u32, n: u64, out: *mut u8,
+                                  cap: usize, len: *mut usize, frame_off: *mut u64, sigs: *mut u8) -> c_int;
+    pub fn pbft_replica_set_signing_seed(r: *mut pbft_replica, seed: *const u8) -> c_int;
+    pub fn pbft_replica_set_signer(r: *mut pbft_replica, f: pbft_signer_fn, user: *mut c_void) -> c_int;
+    pub fn pbft_replica_emit_frames(r: *mut pbft_replica, flags: u32, out: *mut u8, cap: usize, len: *mut usize,
+                                    n_votes: *mut u64) -> c_int;
+    pub fn pbft_replica_get_egress_stats(r: *mut pbft_replica, out: *mut pbft_replica_egress_stats) -> c_int;
 }

@@ -483,6 +483,37 @@ impl GpuVerifier {
             sig
         }).collect())
     }
+    /// Install this context's signing identity (pbft_sign_set_seed): the seed is expanded once on the device;
+    /// `replica` is the index the frames carry.  Returns the public key.  `None` clears it.
+    pub fn set_signing_seed(&mut self, seed: Option<&[u8; 32]>, replica: u32) -> Result<[u8; 32]> {
+        let mut public = [0u8; 32];
+        check(unsafe {
+            ffi::pbft_sign_set_seed(self.ctx, seed.map_or(ptr::null(), |s| s.as_ptr()), replica, public.as_mut_ptr())
+        })?;
+        Ok(public)
+    }
+    /// The envelopes signed with the installed seed and written as UviBytes/JSON vote frames on the GPU
+    /// (pbft_sign_votes_frames): (stream, frame offsets [n + 1], signatures).
+    pub fn sign_votes_frames(&mut self, envelopes: &[Envelope]) -> Result<(Vec<u8>, Vec<u64>, Vec<[u8; 64]>)> {
+        let n = envelopes.len();
+        let env = envelopes.as_ptr() as *const u8;
+        let stride = ffi::PBFT_ENVELOPE_BYTES as u32;
+        let mut len = 0usize;
+        unsafe {
+            // the size query: PBFT_EINVAL with the length needed, unless there is nothing to write
+            ffi::pbft_sign_votes_frames(self.ctx, env, stride, n as u64, ptr::null_mut(), 0, &mut len, ptr::null_mut(),
+                                        ptr::null_mut());
+        }
+        let mut out = vec![0u8; len];
+        let mut off = vec![0u64; n + 1];
+        let mut sigs = vec![[0u8; 64]; n];
+        check(unsafe {
+            ffi::pbft_sign_votes_frames(self.ctx, env, stride, n as u64, out.as_mut_ptr(), out.len(), &mut len,
+                                        off.as_mut_ptr(), sigs.as_mut_ptr() as *mut u8)
+        })?;
+        out.truncate(len);
+        Ok((out, off, sigs))
+    }
     pub fn raw(&self) -> *mut ffi::pbft_ctx {
         self.ctx
     }
@@ -839,6 +870,34 @@ impl<'a> Replica<'a> {
     /// (pbft_replica_set_streams_pp; default on).  Off: every PrePrepare goes through the general parser.
     pub fn set_streams_pp(&mut self, on: bool) -> Result<()> {
         check(unsafe { ffi::pbft_replica_set_streams_pp(self.raw, on as c_int) }).map(|_| ())
+    }
+    /// The replica signs its own votes on the GPU (pbft_replica_set_signing_seed): the seed's public key must be
+    /// keys[self_id]; turns the outbox on.  `None` clears the seed.
+    pub fn set_signing_seed(&mut self, seed: Option<&[u8; 32]>) -> Result<()> {
+        check(unsafe {
+            ffi::pbft_replica_set_signing_seed(self.raw, seed.map_or(ptr::null(), |s| s.as_ptr()))
+        }).map(|_| ())
+    }
+    /// Sign and encode every vote the decided events oblige this replica to send (pbft_replica_emit_frames): the
+    /// bytes to write to every connected peer, and the number of votes.  `loopback`: the votes are also pushed as
+    /// this replica's own (verified in the next flush).
+    pub fn emit_frames(&mut self, loopback: bool) -> Result<(Vec<u8>, u64)> {
+        let flags = if loopback { ffi::PBFT_EMIT_LOOPBACK } else { 0 };
+        let (mut len, mut votes) = (0usize, 0u64);
+        check(unsafe { ffi::pbft_replica_emit_frames(self.raw, 0, ptr::null_mut(), 0, &mut len, &mut votes) })?;
+        let mut out = vec![0u8; len];
+        if len > 0 {
+            check(unsafe {
+                ffi::pbft_replica_emit_frames(self.raw, flags, out.as_mut_ptr(), out.len(), &mut len, &mut votes)
+            })?;
+            out.truncate(len);
+        }
+        Ok((out, votes))
+    }
+    pub fn egress_stats(&self) -> ffi::pbft_replica_egress_stats {
+        let mut s = ffi::pbft_replica_egress_stats::default();
+        unsafe { ffi::pbft_replica_get_egress_stats(self.raw, &mut s) };
+        s
     }
     pub fn pp_stats(&self) -> ffi::pbft_replica_pp_stats {
         let mut s = ffi::pbft_replica_pp_stats::default();

@@ -31,7 +31,9 @@ EXPORTS = (
     "pbft_wire_index_streams_device", "pbft_index_reserve", "pbft_verify_streams_tally_device",
     "pbft_verify_streams_tally", "pbft_admit_device", "pbft_admit_reserve", "pbft_verify_streams_admit",
     "pbft_streams_admit_reserve", "pbft_wire_decode_preprepare", "pbft_wire_decode_preprepares_device",
-    "pbft_verify_streams_admit_pp",
+    "pbft_verify_streams_admit_pp", "pbft_egress_reserve", "pbft_sign_votes_frames_device", "pbft_sign_votes_frames",
+    # include/pbft_verify.h, egress
+    "pbft_sign_set_seed",
 )
 
 ERRORS = {0: "PBFT_OK", -1: "PBFT_EINVAL", -2: "PBFT_EHIP", -3: "PBFT_ENOKEYS",
@@ -146,6 +148,10 @@ def load() -> ctypes.CDLL:
         "pbft_wire_decode_preprepares_device": (i32, [vp, vp, u64, vp, vp, u32, vp, vp]),
         "pbft_verify_streams_admit_pp": (i32, [vp, vp, u64, vp, vp, vp, u32, u32, u64, u32, u32, u64, u64, u64, vp, vp,
                                                vp, vp, vp, vp, vp, vp, vp, vp]),
+        "pbft_sign_set_seed": (i32, [vp, vp, u32, vp]),
+        "pbft_egress_reserve": (i32, [vp, u64]),
+        "pbft_sign_votes_frames_device": (i32, [vp, vp, u32, u64, vp, u64, vp, vp, vp]),
+        "pbft_sign_votes_frames": (i32, [vp, vp, u32, u64, vp, ctypes.c_size_t, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

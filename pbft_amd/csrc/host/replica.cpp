@@ -46,6 +46,7 @@
 #include "../../../include/pbft_wire.h"
 #include "../admit_core.h"
 #include "../wire_decode_core.h"
+#include "../egress_core.h"
 
 // The device half of pbft_replica_push_streams lives in the GPU library (pbft_verify.hip).  Weak, so that this file
 // still links on its own into the host-only programs that test the state machine: there the symbols are null and a
@@ -56,6 +57,11 @@
 // pbft_replica_push_streams takes the general parser, as with pbft_replica_set_streams_pp(r, 0).
 #pragma weak pbft_verify_streams_admit_pp
 #pragma weak pbft_wire_decode_preprepare
+// ... and the signer of the replica's own votes (egress.hip): without it pbft_replica_set_signing_seed reports
+// PBFT_ENODEV and only a signer override (pbft_replica_set_signer) emits.
+#pragma weak pbft_sign_set_seed
+#pragma weak pbft_sign_votes_frames
+#pragma weak pbft_sign_batch
 
 namespace {
 
@@ -536,6 +542,15 @@ struct pbft_replica {
   pbft_replica_streams_stats sstats{};
   bool streams_pp = true;  // pbft_replica_set_streams_pp
   pbft_replica_pp_stats ppstats{};
+  // egress: the envelopes of the votes the decided events oblige this replica to send ([k][85], event order), kept
+  // while a signer is installed (pbft_replica_set_signing_seed on dctx, or pbft_replica_set_signer)
+  bool outbox_on = false;
+  bool seed_set = false;
+  pbft_signer_fn signer_fn = nullptr;
+  void* signer_user = nullptr;
+  std::vector<uint8_t> outbox;
+  std::vector<uint8_t> out_sigs;  // pbft_replica_emit_frames: the signatures of the call (loopback)
+  pbft_replica_egress_stats estats{};
 };
 
 static uint32_t primary_of(const pbft_replica* r, uint64_t view) { return (uint32_t)(view % r->n); }
@@ -952,15 +967,25 @@ static void gc(pbft_replica* r) {
 
 // The events one window's state now decides (pre-prepared, prepared :177-182, committed_local :214-223), appended
 // to `out`; a committed window drops its stragglers (nothing of it may be in flight: callers guarantee that).
+// `ob` (null while the outbox is off): the envelope of the vote each event obliges the replica to send is appended
+// there, with the window's digest as it is now -- the window may be gone before the caller emits.
+static void outbox_append(std::vector<uint8_t>* ob, uint8_t kind, uint64_t view, uint64_t seq, const Window& w) {
+  if (!ob) return;
+  ob->resize(ob->size() + PBFT_ENVELOPE_BYTES);
+  pbft_envelope(ob->data() + ob->size() - PBFT_ENVELOPE_BYTES, kind, view, seq, w.digest.data());
+}
 template <class Out>
-static void evaluate_window(const pbft_replica* r, uint64_t view, uint64_t seq, Window& w, Out& out) {
+static void evaluate_window(const pbft_replica* r, uint64_t view, uint64_t seq, Window& w, Out& out,
+                            std::vector<uint8_t>* ob) {
   if (!w.pre_prepared_reported && w.have_pre_prepare) {
     w.pre_prepared_reported = true;
     out.push_back({view, seq, PBFT_EVENT_PRE_PREPARED});
+    outbox_append(ob, PBFT_KIND_PREPARE, view, seq, w);
   }
   if (!w.prepared_reported && is_prepared(r, view, w)) {
     w.prepared_reported = true;
     out.push_back({view, seq, PBFT_EVENT_PREPARED});
+    outbox_append(ob, PBFT_KIND_COMMIT, view, seq, w);
   }
   if (!w.committed_reported && is_committed_local(r, view, w)) {
     w.committed_reported = true;
@@ -979,7 +1004,7 @@ static void evaluate(pbft_replica* r) {
     Window* w = find_window(r, r->current_view, q);
     if (!w || !w->dirty) continue;  // (gone, or already evaluated: a duplicate entry)
     w->dirty = false;
-    evaluate_window(r, r->current_view, q, *w, r->evq);
+    evaluate_window(r, r->current_view, q, *w, r->evq, r->outbox_on ? &r->outbox : nullptr);
   }
   r->dirty.clear();
 }
@@ -1044,7 +1069,7 @@ static void prefetch_phase(const Phase& p) {
   if (!p.digs.empty()) prefetch_bytes(p.digs.data(), 64);
 }
 static void apply_range(pbft_replica* r, size_t s0, size_t s1, uint64_t st_out[3], uint8_t* touched,
-                        std::vector<pbft_round_event>& events) {
+                        std::vector<pbft_round_event>& events, std::vector<uint8_t>* ob) {
   std::vector<int64_t> amap;
   std::vector<uint8_t> mism;
   uint64_t st[3] = {0, 0, 0};  // local: the threads' st_out entries share cache lines
@@ -1146,7 +1171,7 @@ static void apply_range(pbft_replica* r, size_t s0, size_t s1, uint64_t st_out[3
       bool any = false;
       for (size_t gj = gi + 1; gj-- > 0 && r->segs[gj].key == g.key;) any = any || touched[gj];
       // (not while signer sets wait for the same flush_poll: the window is evaluated once, after both)
-      if (any && !r->defer_eval) evaluate_window(r, g.key.first, g.key.second, w, events);
+      if (any && !r->defer_eval) evaluate_window(r, g.key.first, g.key.second, w, events, ob);
     }
   }
   release_counts(r, rel);
@@ -1173,8 +1198,9 @@ static void apply_segs(pbft_replica* r, size_t s0, size_t s1) {
   const size_t C = T <= 1 ? 1 : std::min<size_t>(4 * T, s1 - s0);
   std::vector<std::array<uint64_t, 3>> st(C, {0, 0, 0});
   std::vector<std::vector<pbft_round_event>> ev(C);
+  std::vector<std::vector<uint8_t>> ob(r->outbox_on ? C : 0);  // the pieces' own-vote envelopes, like their events
   if (T <= 1) {
-    apply_range(r, s0, s1, st[0].data(), r->touched.data(), ev[0]);
+    apply_range(r, s0, s1, st[0].data(), r->touched.data(), ev[0], r->outbox_on ? &ob[0] : nullptr);
   } else {
     std::vector<size_t> cut(C + 1, s1);
     cut[0] = s0;
@@ -1189,14 +1215,17 @@ static void apply_segs(pbft_replica* r, size_t s0, size_t s1) {
       for (size_t c; (c = next.fetch_add(1, std::memory_order_relaxed)) < C;) {
         if (cut[c + 1] > cut[c]) {
           std::vector<pbft_round_event> e;  // (local: the pieces' vectors share cache lines)
-          apply_range(r, cut[c], cut[c + 1], st[c].data(), r->touched.data(), e);
+          std::vector<uint8_t> o;
+          apply_range(r, cut[c], cut[c + 1], st[c].data(), r->touched.data(), e, r->outbox_on ? &o : nullptr);
           ev[c] = std::move(e);
+          if (r->outbox_on) ob[c] = std::move(o);
         }
         done.fetch_add(1, std::memory_order_release);
       }
     }, [&] { return done.load(std::memory_order_acquire) == C; });
   }
   for (const auto& e : ev) r->evq.insert(r->evq.end(), e.begin(), e.end());
+  for (const auto& o : ob) r->outbox.insert(r->outbox.end(), o.begin(), o.end());
   for (const auto& c : st) {
     r->stats.accepted += c[0];
     r->stats.rejected_sig += c[1];
@@ -3089,6 +3118,99 @@ int pbft_replica_reserve_streams(pbft_replica* r, uint64_t max_stream_bytes, uin
 int pbft_replica_set_streams_pp(pbft_replica* r, int on) {
   if (!r) return PBFT_EINVAL;
   r->streams_pp = on != 0;
+  return PBFT_OK;
+}
+
+// ---- egress: the replica's own votes (include/pbft_replica.h) ----
+static void outbox_switch(pbft_replica* r) {
+  r->outbox_on = r->seed_set || r->signer_fn;
+  if (!r->outbox_on) r->outbox.clear();
+}
+
+int pbft_replica_set_signing_seed(pbft_replica* r, const uint8_t* seed) {
+  if (!r) return PBFT_EINVAL;
+  if (!seed) {
+    if (r->seed_set && r->dctx && pbft_sign_set_seed) (void)pbft_sign_set_seed(r->dctx, nullptr, 0, nullptr);
+    r->seed_set = false;
+    outbox_switch(r);
+    return PBFT_OK;
+  }
+  if (!r->ctx) return PBFT_EINVAL;
+  if (!pbft_sign_set_seed || !pbft_sign_batch) return PBFT_ENODEV;
+  int rc;
+  if (!r->dctx && (rc = pbft_verify_ctx_clone(r->ctx, &r->dctx)) != PBFT_OK) {
+    r->dctx = nullptr;
+    return rc;
+  }
+  // the seed's public key, before anything is installed: a wrong seed changes nothing
+  uint8_t pub[32];
+  if ((rc = pbft_sign_batch(r->dctx, seed, 1, nullptr, nullptr, 0, 0, 0, nullptr, nullptr, pub)) != PBFT_OK) return rc;
+  if (memcmp(pub, r->keys.data() + 32 * (size_t)r->self, 32) != 0) return PBFT_EINVAL;
+  if ((rc = pbft_sign_set_seed(r->dctx, seed, r->self, pub)) != PBFT_OK) return rc;
+  r->seed_set = true;
+  outbox_switch(r);
+  return PBFT_OK;
+}
+
+int pbft_replica_set_signer(pbft_replica* r, pbft_signer_fn fn, void* user) {
+  if (!r) return PBFT_EINVAL;
+  r->signer_fn = fn;
+  r->signer_user = fn ? user : nullptr;
+  outbox_switch(r);
+  return PBFT_OK;
+}
+
+int pbft_replica_emit_frames(pbft_replica* r, uint32_t flags, uint8_t* out, size_t cap, size_t* len,
+                             uint64_t* n_votes) {
+  if (!r || (flags & ~PBFT_EMIT_LOOPBACK) || (cap && !out)) return PBFT_EINVAL;
+  if (len) *len = 0;
+  if (n_votes) *n_votes = 0;
+  const uint64_t N = r->outbox.size() / PBFT_ENVELOPE_BYTES;
+  if (!r->outbox_on || N == 0) return PBFT_OK;
+  const auto t0 = std::chrono::steady_clock::now();
+  size_t need = 0;
+  for (uint64_t i = 0; i < N; ++i) need += pbft::eg_env_frame_len(r->outbox.data() + PBFT_ENVELOPE_BYTES * i, r->self);
+  if (len) *len = need;
+  if (!out && cap == 0) return PBFT_OK;  // the size query
+  if (cap < need) return PBFT_EINVAL;
+  r->out_sigs.resize(64 * (size_t)N);
+  size_t got = 0;
+  int rc;
+  if (r->signer_fn) {
+    rc = r->signer_fn(r->signer_user, r->outbox.data(), N, r->self, out, cap, &got, r->out_sigs.data());
+    if (rc == PBFT_OK && got != need) rc = PBFT_EINVAL;  // (not the canonical frames)
+  } else {
+    if (!pbft_sign_votes_frames) return PBFT_ENODEV;
+    rc = pbft_sign_votes_frames(r->dctx, r->outbox.data(), PBFT_ENVELOPE_BYTES, N, out, cap, &got, nullptr,
+                                r->out_sigs.data());
+  }
+  if (rc != PBFT_OK) {
+    if (len) *len = 0;
+    return rc;
+  }
+  if (flags & PBFT_EMIT_LOOPBACK) {
+    std::vector<uint8_t> envs;
+    envs.swap(r->outbox);  // (a push decides no event, but the outbox is this call's to drain)
+    for (uint64_t i = 0; i < N; ++i) {
+      const uint8_t* e = envs.data() + PBFT_ENVELOPE_BYTES * i;
+      if (pbft_replica_push(r, e[4], pbft::eg_le64(e + 5), pbft::eg_le64(e + 13), e + 21, r->self,
+                            r->out_sigs.data() + 64 * i) == 1)
+        ++r->estats.loopback_pushed;
+    }
+  }
+  r->outbox.clear();
+  if (len) *len = got;
+  if (n_votes) *n_votes = N;
+  r->estats.emitted += N;
+  ++r->estats.calls;
+  r->estats.emit_ns += ns_since(t0);
+  return PBFT_OK;
+}
+
+int pbft_replica_get_egress_stats(pbft_replica* r, pbft_replica_egress_stats* out) {
+  if (!r || !out) return PBFT_EINVAL;
+  *out = r->estats;
+  out->queued = r->outbox.size() / PBFT_ENVELOPE_BYTES;
   return PBFT_OK;
 }
 

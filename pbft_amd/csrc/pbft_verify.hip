@@ -40,6 +40,7 @@ using namespace pbft;
 #include "wire_decode_kernels.h"
 #include "wire_index_kernels.h"
 #include "wire_pp_kernels.h"
+#include "egress_kernels.h"
 // Finish configuration by batch size (signatures per lane, product tree, waves per SIMD), measured on MI355X
 // with the lane-parallel wave inversion (profiles/r03/ab_finish.txt): 131k 0.2115 -> 0.1906 ms (width 2),
 // 262k 0.3628 -> 0.3429 (width 4), 2^20 finish kernel 118.6 -> 91.4 us (width 8, tree, 2 waves per SIMD).
@@ -260,6 +261,18 @@ struct pbft_ctx {
   // pbft_admit_device: the two key planes, the residue marks and their prefix (grow-only; pbft_admit_reserve)
   uint8_t* d_admit = nullptr;
   size_t admit_cap = 0;  // bytes
+  // pbft_sign_set_seed: the expanded signing key a | prefix | A and the replica index (egress_kernels.h), device
+  // resident; pbft_sign_votes_frames_device: the tile sums (grow-only; pbft_egress_reserve); the blocking form's
+  // device buffers (grow-only); the signing kernel's form (PBFT_OPT_EGRESS_BLOCK / _DIRECT)
+  uint32_t* d_sign_key = nullptr;
+  bool sign_set = false;
+  uint32_t sign_replica = 0;
+  uint8_t* d_egress = nullptr;
+  size_t egress_cap = 0;  // bytes
+  uint8_t* d_egress_io = nullptr;
+  size_t egress_io_cap = 0;  // bytes
+  int egress_block = 64;
+  bool egress_direct = false;
 };
 
 #ifndef PBFT_ENV_SCHED
@@ -1042,6 +1055,12 @@ int pbft_verify_ctx_destroy(pbft_ctx* c) {
   (void)hipFree(c->d_group);
   (void)hipFree(c->d_index);
   (void)hipFree(c->d_admit);
+  if (c->d_sign_key) {
+    (void)hipMemset(c->d_sign_key, 0, 4 * EGRESS_KEY_WORDS);
+    (void)hipFree(c->d_sign_key);
+  }
+  (void)hipFree(c->d_egress);
+  (void)hipFree(c->d_egress_io);
   if (c->h_bitmap) (void)hipHostFree(c->h_bitmap);
   if (c->h_stage) (void)hipHostFree(c->h_stage);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -2905,6 +2924,114 @@ int pbft_sign_batch(pbft_ctx* c, const uint8_t* seeds, uint32_t n_seeds, const u
   return PBFT_OK;
 }
 
+// ---- replica egress: the round's own votes signed and framed on the device (include/pbft_wire.h; egress.hip) ----
+int pbft_sign_set_seed(pbft_ctx* c, const uint8_t* seed, uint32_t replica, uint8_t* pub_out) {
+  if (!c) return set_err(PBFT_EINVAL, "null context");
+  if (seed && replica > pbft::EG_MAX_REPLICA) return set_err(PBFT_EINVAL, "replica index above 65535");
+  if (c->in_flight) return set_err(PBFT_EBUSY, "async batch in flight");
+  HIP_TRY(hipSetDevice(c->device));
+  if (!seed) {
+    c->sign_set = false;
+    if (c->d_sign_key) {
+      HIP_TRY(hipMemsetAsync(c->d_sign_key, 0, 4 * EGRESS_KEY_WORDS, c->stream));
+      HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    return PBFT_OK;
+  }
+  if (!c->d_sign_key) {
+    if (hipMalloc(&c->d_sign_key, 4 * EGRESS_KEY_WORDS) != hipSuccess) return set_err(PBFT_ENOMEM, "signing key alloc");
+    HIP_TRY(hipMemsetAsync(c->d_sign_key, 0, 4 * EGRESS_KEY_WORDS, c->stream));
+  }
+  c->sign_set = false;
+  HIP_TRY(hipMemcpyAsync(c->d_sign_key + EGRESS_KEY_SEED, seed, 32, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(launch_egress_seed(c->d_sign_key, replica, c->d_tabB, c->stream));  // (zeroes the staged seed)
+  uint8_t pub[32];
+  HIP_TRY(hipMemcpyAsync(pub, c->d_sign_key + 16, 32, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (pub_out) memcpy(pub_out, pub, 32);
+  c->sign_set = true;
+  c->sign_replica = replica;
+  return PBFT_OK;
+}
+
+static int ensure_egress(pbft_ctx* c, uint64_t N) {
+  const size_t bytes = egress_ws_bytes(N ? N : 1);
+  if (bytes <= c->egress_cap) return PBFT_OK;
+  if (c->d_egress) HIP_TRY(hipFree(c->d_egress));  // (waits for the device: an earlier call may still use it)
+  c->d_egress = nullptr;
+  c->egress_cap = 0;
+  if (hipMalloc(&c->d_egress, bytes) != hipSuccess) return set_err(PBFT_ENOMEM, "egress workspace alloc");
+  c->egress_cap = bytes;
+  return PBFT_OK;
+}
+
+int pbft_egress_reserve(pbft_ctx* c, uint64_t max_n) {
+  if (!c) return set_err(PBFT_EINVAL, "null context");
+  if (max_n > pbft::EG_MAX_N) return set_err(PBFT_EINVAL, "more than 2^24 votes to sign");
+  HIP_TRY(hipSetDevice(c->device));
+  return ensure_egress(c, max_n);
+}
+
+int pbft_sign_votes_frames_device(pbft_ctx* c, const uint8_t* d_env, uint32_t env_stride, uint64_t N, uint8_t* d_out,
+                                  uint64_t out_cap, uint64_t* d_frame_off, uint8_t* d_sigs, void* stream) {
+  if (!c) return set_err(PBFT_EINVAL, "null context");
+  if (!c->sign_set) return set_err(PBFT_EINVAL, "no signing seed (pbft_sign_set_seed)");
+  if (N > pbft::EG_MAX_N) return set_err(PBFT_EINVAL, "more than 2^24 votes to sign");
+  if (!d_frame_off || (N && !d_env) || (out_cap && !d_out) || (N && env_stride < pbft::EG_ENV_BYTES))
+    return set_err(PBFT_EINVAL, "bad egress argument");
+  if (((uintptr_t)d_frame_off & 7) || ((uintptr_t)d_sigs & 3)) return set_err(PBFT_EINVAL, "misaligned egress pointer");
+  HIP_TRY(hipSetDevice(c->device));
+  int rc = ensure_egress(c, N);
+  if (rc) return rc;
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  HIP_TRY(launch_egress(d_env, env_stride, N, c->d_sign_key, c->d_tabB, (uint64_t*)c->d_egress, d_out, out_cap,
+                        d_frame_off, d_sigs, c->egress_block, c->egress_direct, st));
+  return PBFT_OK;
+}
+
+int pbft_sign_votes_frames(pbft_ctx* c, const uint8_t* envelopes, uint32_t env_stride, uint64_t N, uint8_t* out,
+                           size_t cap, size_t* len, uint64_t* frame_off, uint8_t* sigs) {
+  if (!c || !len) return set_err(PBFT_EINVAL, "null egress argument");
+  *len = 0;
+  if (!c->sign_set) return set_err(PBFT_EINVAL, "no signing seed (pbft_sign_set_seed)");
+  if (N > pbft::EG_MAX_N) return set_err(PBFT_EINVAL, "more than 2^24 votes to sign");
+  if ((N && (!envelopes || env_stride < pbft::EG_ENV_BYTES)) || (cap && !out))
+    return set_err(PBFT_EINVAL, "bad egress argument");
+  if (c->in_flight) return set_err(PBFT_EBUSY, "async batch in flight");
+  size_t need = 0;  // the layout is a function of the envelopes and the replica index: known before anything runs
+  for (uint64_t i = 0; i < N; ++i) need += pbft::eg_env_frame_len(envelopes + (size_t)env_stride * i, c->sign_replica);
+  *len = need;
+  if (need > cap) return set_err(PBFT_EINVAL, "output buffer too small for the frames");
+  if (N == 0) {
+    if (frame_off) frame_off[0] = 0;
+    return PBFT_OK;
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t env_bytes = (size_t)env_stride * (N - 1) + pbft::EG_ENV_BYTES;
+  const size_t offF = up(env_bytes), offS = offF + up(8 * (size_t)(N + 1)), offO = offS + up(64 * (size_t)N);
+  const size_t total = offO + up(need);
+  if (total > c->egress_io_cap) {
+    if (c->d_egress_io) HIP_TRY(hipFree(c->d_egress_io));
+    c->d_egress_io = nullptr;
+    c->egress_io_cap = 0;
+    if (hipMalloc(&c->d_egress_io, total) != hipSuccess) return set_err(PBFT_ENOMEM, "egress buffers alloc");
+    c->egress_io_cap = total;
+  }
+  int rc = ensure_egress(c, N);
+  if (rc) return rc;
+  uint8_t* d = c->d_egress_io;
+  HIP_TRY(hipMemcpyAsync(d, envelopes, env_bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(launch_egress(d, env_stride, N, c->d_sign_key, c->d_tabB, (uint64_t*)c->d_egress, d + offO, need,
+                        (uint64_t*)(d + offF), sigs ? d + offS : nullptr, c->egress_block, c->egress_direct,
+                        c->stream));
+  if (need) HIP_TRY(hipMemcpyAsync(out, d + offO, need, hipMemcpyDeviceToHost, c->stream));
+  if (frame_off) HIP_TRY(hipMemcpyAsync(frame_off, d + offF, 8 * (size_t)(N + 1), hipMemcpyDeviceToHost, c->stream));
+  if (sigs) HIP_TRY(hipMemcpyAsync(sigs, d + offS, 64 * (size_t)N, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return PBFT_OK;
+}
+
 int pbft_verify_reserve(pbft_ctx* c, uint64_t max_n) {
   if (!c) return set_err(PBFT_EINVAL, "null context");
   HIP_TRY(hipSetDevice(c->device));
@@ -2949,6 +3076,14 @@ int pbft_verify_set_option(pbft_ctx* c, int option, uint64_t value) {
       if (value < pbft::IX_TILE_MIN || value > INDEX_TILE_DEFAULT || (value & (value - 1)))
         return set_err(PBFT_EINVAL, "index tile bytes");
       c->index_tile = (uint32_t)value;
+      return PBFT_OK;
+    case PBFT_OPT_EGRESS_BLOCK:
+      if (value != 0 && value != 64 && value != 256) return set_err(PBFT_EINVAL, "egress block is 64 or 256");
+      c->egress_block = value ? (int)value : 64;
+      return PBFT_OK;
+    case PBFT_OPT_EGRESS_DIRECT:
+      if (value > 1) return set_err(PBFT_EINVAL, "egress direct is 0 or 1");
+      c->egress_direct = value == 1;
       return PBFT_OK;
   }
   return set_err(PBFT_EINVAL, "unknown option");

@@ -625,6 +625,7 @@ class GpuBatchVerifier:
                                           d_n_res or None, stream or None))
 
     OPT_INDEX_TILE = 19
+    OPT_EGRESS_BLOCK, OPT_EGRESS_DIRECT = 20, 21
     OPT_GROUP_SEED, OPT_GROUP_HASH_BITS = 16, 17
     OPT_SPLIT_BELOW, OPT_FINISH_WIDTH, OPT_KEY_TABLE_BUDGET_MB, OPT_FINISH_TREE, OPT_LAT_SPLIT = 1, 2, 3, 4, 5
     OPT_KERNEL_TIMING = 7
@@ -680,6 +681,47 @@ class GpuBatchVerifier:
         check(self._lib.pbft_sign_batch(self._ctx, _ptr(seeds), len(seeds), _ptr(seed_idx), _ptr(msg), msg_len,
                                         msg.shape[1], n, _ptr(R), _ptr(S), _ptr(pub)))
         return R, S, pub
+
+    # -- egress: this replica's own votes, signed and framed on the GPU (include/pbft_wire.h) ------
+    def set_signing_seed(self, seed, replica: int = 0) -> np.ndarray:
+        """pbft_sign_set_seed: expand `seed` (32 bytes; None clears) once into the context's device-resident signing
+        key; `replica` is the index the frames carry.  Returns the public key (zeros after a clear)."""
+        pub = np.zeros(32, dtype=np.uint8)
+        if seed is None:
+            check(self._lib.pbft_sign_set_seed(self._ctx, None, 0, None))
+            return pub
+        sd = np.frombuffer(bytes(seed), dtype=np.uint8).copy()
+        assert sd.size == 32
+        check(self._lib.pbft_sign_set_seed(self._ctx, _ptr(sd), replica, _ptr(pub)))
+        return pub
+
+    def egress_reserve(self, max_n: int) -> None:
+        """pbft_egress_reserve: pre-size the egress workspace (required before capturing sign_votes_frames_device
+        into a graph)."""
+        check(self._lib.pbft_egress_reserve(self._ctx, max_n))
+
+    def sign_votes_frames(self, envelopes, env_stride: int = 85, with_sigs: bool = True):
+        """pbft_sign_votes_frames: N envelopes (host, row i at i * env_stride) -> (stream, frame_off [N + 1], sigs
+        [N][64] or None): the signed votes' UviBytes frames, what wire.encode_votes writes for them."""
+        env = np.ascontiguousarray(envelopes, dtype=np.uint8).reshape(-1)
+        n = 0 if env.size == 0 else (env.size - 85) // env_stride + 1
+        need = ctypes.c_size_t()
+        args = (self._ctx, _ptr(env) if n else None, env_stride, n)
+        self._lib.pbft_sign_votes_frames(*args, None, 0, ctypes.byref(need), None, None)  # the size query
+        out = np.zeros(max(need.value, 1), dtype=np.uint8)
+        off = np.zeros(n + 1, dtype=np.uint64)
+        sigs = np.zeros((n, 64), dtype=np.uint8) if with_sigs else None
+        check(self._lib.pbft_sign_votes_frames(*args, _ptr(out), need.value, ctypes.byref(need), _ptr(off),
+                                               _ptr(sigs) if with_sigs and n else None))
+        return out[:need.value], off, sigs
+
+    def sign_votes_frames_device(self, d_env: int, n: int, d_out: int, out_cap: int, d_frame_off: int,
+                                 d_sigs: int = 0, env_stride: int = 85, stream: int = 0) -> None:
+        """pbft_sign_votes_frames_device: enqueue only (raw device pointers): n envelopes at d_env -> the frames at
+        d_out (any alignment, at most out_cap bytes, whole frames only), d_frame_off [n + 1] u64 and, if given,
+        d_sigs [n][64]."""
+        check(self._lib.pbft_sign_votes_frames_device(self._ctx, d_env or None, env_stride, n, d_out or None, out_cap,
+                                                      d_frame_off or None, d_sigs or None, stream or None))
 
     def close(self):
         if self._ctx:
