@@ -5,7 +5,8 @@
 // (measured on MI355X: ~1.3x the issue cost of a 32-bit VOP3 op),
 // so a multiply is 100 mads + one 64-bit carry chain; a square is 55 mads.
 //
-// Bounds discipline (checked by tools/limb_bounds.py):
+// Bounds discipline (checked by tools/limb_bounds.py as intervals, and by tests/test_arith.py on the host build and
+// tests/test_gpu_arith.py on the gfx950 build by running every op with its operands' limbs at those bounds):
 //  * "carried"  : output of fe_mul/fe_sq/fe_carry: limbs <= 2^26 / 2^25 (+2^14 slack)
 //  * fe_add     : no carry; inputs carried -> limbs <= 2^27
 //  * fe_sub     : f + 2p - g; g must be carried; result limbs <= 3*2^26

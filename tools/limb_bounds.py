@@ -3,6 +3,10 @@
 Checks that no 64-bit column accumulator of fe_mul/fe_sq can overflow and that
 every u32 limb stays below 2^32, for the exact add/sub/mul sequence used by the
 mixed addition (comb step) and doubling.  Run: python tools/limb_bounds.py
+
+Importable: the bound vectors (CARRIED, P2), the interval operations (add, sub, mulmax) and the operand bounds of
+every product of the comb step (MADD_PRODUCTS) and of the doubling (DBL_PRODUCTS).  tests/arith_cases.py takes every
+operand bound from here and runs the code with its limbs at them.
 """
 import math
 E26, E25 = 1 << 26, 1 << 25
@@ -59,31 +63,53 @@ def chain1(cols):
         assert x <= b, "chain1 overshoot"
 
 C = CARRIED
-# mixed add (comb step): P3 + halved affine Niels ((y+x)/2, (y-x)/2, dxy) with canonical table limbs
-ymx = sub(C, C, P2); ypx = add(C, C)
-print("madd a=(Y-X)*ymx   log2 max col:", mulmax(ymx, C))
-print("madd b=(Y+X)*ypx   log2 max col:", mulmax(ypx, C))
-d = C   # D = Z1: halved table entries (ge25519.h), no doubling of Z1
-e = sub(C, C, P2); f = sub(d, C, P2); g = add(d, C); h = add(C, C)
-# operand order as coded in ge25519.h: the second operand is the one premultiplied by 19
-for neg in (False, True):
-    F, G = (g, f) if neg else (f, g)   # negative digit swaps d-c and d+c
-    for nm, (x, y) in {"X3=F*E": (F, e), "Y3=G*H": (G, h), "Z3=dmc*dpc": (f, g), "T3=E*H": (e, h)}.items():
-        print("madd neg=%d" % neg, nm, " log2 max col:", mulmax(x, y))
-# madd v2 (PBFT_MADD_V2, verify_core.h): k' = +-k (2p - k for a negative digit), F = D - c, G = D + c never
-# swap; X3 = F*E, T3 = H*E, Y3 = H*G, Z3 = F*G (second operand premultiplied by 19)
-for neg in (False, True):
-    kk = P2 if neg else C            # 2p - k <= 2p limb-wise (k canonical)
-    print("madd v2 neg=%d c=T*k'" % neg, " log2 max col:", mulmax(C, kk))
-e = sub(C, C, P2); F = sub(d, C, P2); G = add(d, C); h = add(C, C)
-for nm, (x, y) in {"X3=F*E": (F, e), "T3=H*E": (h, e), "Y3=H*G": (h, G), "Z3=F*G": (F, G)}.items():
-    print("madd v2", nm, " log2 max col:", mulmax(x, y))
-# doubling (dbl-2008-hwcd, a=-1): A=X^2, B=Y^2, C2=2Z^2, H=A+B, E=H-(X+Y)^2, G=A-B, F=C2+G
-xy = add(C, C)
-print("dbl (X+Y)^2         log2 max col:", mulmax(xy, xy))
-print("sq of carried       log2 max col:", mulmax(C, C))
-# precomputation-only doubling: E, F, G, H are carried before the products
-H = C; E = C; G = C; F = C
-for nm, (x, y) in {"X=E*F": (E, F), "Y=G*H": (G, H), "T=E*H": (E, H), "Z=F*G": (F, G)}.items():
-    print("dbl", nm, " log2 max col:", mulmax(x, y))
-print("all bounds OK")
+TABLE = [E26 - 1 if i % 2 == 0 else E25 - 1 for i in range(10)]   # canonical limbs (comb table entries)
+# madd v2 (PBFT_MADD_V2, verify_core.h ge_madd_ab), the comb step on P = (X, Y, Z, T) carried and a canonical entry
+# (qa, qb, k): a = (Y-X) qa, b = (Y+X) qb, c = T k' with k' = +-k (2p - k limb-wise for a negative digit);
+# E = b - a, F = Z - c, G = Z + c, H = b + a; X3 = F*E, T3 = H*E, Y3 = H*G, Z3 = F*G
+YMX = sub(C, C, P2); YPX = add(C, C)
+KK = {False: C, True: P2}        # 2p - k <= 2p limb-wise (k canonical)
+MADD_E = sub(C, C, P2); MADD_F = sub(C, C, P2); MADD_G = add(C, C); MADD_H = add(C, C)
+
+
+def MADD_PRODUCTS(neg):
+    """(first operand bound, second operand bound) of the seven products of one comb step; the second operand is
+    the one premultiplied by 19."""
+    return {"a": (YMX, C), "b": (YPX, C), "c": (C, KK[bool(neg)]), "X3": (MADD_F, MADD_E), "T3": (MADD_H, MADD_E),
+            "Y3": (MADD_H, MADD_G), "Z3": (MADD_F, MADD_G)}
+
+
+# doubling (ge25519.h ge_dbl; dbl-2008-hwcd, a = -1) of carried (X, Y, Z): three squares of carried values, the
+# square of X + Y, and four products of carried E, F, G, H
+DBL_XY = add(C, C)
+DBL_PRODUCTS = {"A": (C, C), "B": (C, C), "C2": (C, C), "XY2": (DBL_XY, DBL_XY),
+                "X": (C, C), "Y": (C, C), "T": (C, C), "Z": (C, C)}
+
+
+def main():
+    # mixed add (comb step): P3 + halved affine Niels ((y+x)/2, (y-x)/2, dxy) with canonical table limbs
+    print("madd a=(Y-X)*ymx   log2 max col:", mulmax(YMX, C))
+    print("madd b=(Y+X)*ypx   log2 max col:", mulmax(YPX, C))
+    # r02 form (PBFT_MADD_V2 = 0): D = Z1 (halved table entries, no doubling of Z1); the second operand is the one
+    # premultiplied by 19
+    e, f, g, h = MADD_E, MADD_F, MADD_G, MADD_H
+    for neg in (False, True):
+        F, G = (g, f) if neg else (f, g)   # negative digit swaps d-c and d+c
+        for nm, (x, y) in {"X3=F*E": (F, e), "Y3=G*H": (G, h), "Z3=dmc*dpc": (f, g), "T3=E*H": (e, h)}.items():
+            print("madd neg=%d" % neg, nm, " log2 max col:", mulmax(x, y))
+    # madd v2: F = D - c, G = D + c never swap
+    for neg in (False, True):
+        print("madd v2 neg=%d c=T*k'" % neg, " log2 max col:", mulmax(*MADD_PRODUCTS(neg)["c"]))
+    for nm, key in {"X3=F*E": "X3", "T3=H*E": "T3", "Y3=H*G": "Y3", "Z3=F*G": "Z3"}.items():
+        print("madd v2", nm, " log2 max col:", mulmax(*MADD_PRODUCTS(False)[key]))
+    # doubling (dbl-2008-hwcd, a=-1): A=X^2, B=Y^2, C2=2Z^2, H=A+B, E=H-(X+Y)^2, G=A-B, F=C2+G
+    print("dbl (X+Y)^2         log2 max col:", mulmax(*DBL_PRODUCTS["XY2"]))
+    print("sq of carried       log2 max col:", mulmax(*DBL_PRODUCTS["A"]))
+    # precomputation-only doubling: E, F, G, H are carried before the products
+    for nm, key in {"X=E*F": "X", "Y=G*H": "Y", "T=E*H": "T", "Z=F*G": "Z"}.items():
+        print("dbl", nm, " log2 max col:", mulmax(*DBL_PRODUCTS[key]))
+    print("all bounds OK")
+
+
+if __name__ == "__main__":
+    main()
