@@ -367,6 +367,48 @@ typedef struct {
 } pbft_replica_egress_stats;
 int pbft_replica_get_egress_stats(pbft_replica *r, pbft_replica_egress_stats *out);
 
+/* ---- the primary's side: client requests in, signed PrePrepare frames out ----
+ * Pbft::add_client_request (src/behavior.rs:63-98): the next sequence number (PrePrepareSequence, src/message.rs:154-172),
+ * the operation's digest, the PrePrepare, its multicast and process_pre_prepare on the PrePrepare itself.  Request i is
+ * operation bytes [op_off[i], op_off[i] + op_len[i]) of ops (which must lie inside ops_bytes: PBFT_EINVAL), timestamp[i]
+ * and the client's address in the 64-byte field clients + 64 * i (include/pbft_wire.h, pbft_wire_encode_preprepares).
+ *
+ * Only the primary of the current view proposes: otherwise PBFT_EINVAL and nothing changes.  Sequence numbers start at
+ * max(next_seq, h + 1), where next_seq is 1 at creation (PrePrepareSequence starts at 0 and increments before use),
+ * moves behind every proposed request and can be set.  Only requests whose sequence number is <= h + log_window are
+ * proposed: *n_proposed may be below N, the rest are the caller's to offer again (counted in held_back).  out receives
+ * the n_proposed frames, byte for byte pbft_wire_encode_preprepares of them with this replica's index, *len their
+ * bytes, *first_seq the first sequence number.  The exact length is known before anything is signed: if cap is smaller,
+ * PBFT_EINVAL, *len, *first_seq and *n_proposed are set and no sequence number is consumed; out = NULL with cap = 0 is
+ * the size query (returns 0, consumes nothing).
+ * The digests, signatures and frames come from the proposer override if one is installed, else from
+ * pbft_sign_preprepares_frames on the replica's signing clone (pbft_replica_set_signing_seed), else PBFT_EINVAL.
+ * pbft_replica_set_proposer: the override, for replicas and tests without a GPU: fn receives the n requests to propose
+ * (the arrays advanced to the first of them), the view, their first sequence number and this replica's index, and
+ * writes the frames to out (cap bytes), *len = their bytes, digests[n][64] and sigs[n][64]; it returns 0 or a negative
+ * code.  fn = NULL removes it.
+ * PBFT_PROPOSE_LOOPBACK: every proposed request is also applied exactly as pbft_replica_on_pre_prepare(r, self_id, view,
+ * seq, op, op_len, digest, sig, NULL) would apply it (the digest is the one just made: nothing is hashed again) -- the
+ * primary's own PrePrepare gates its window and is verified at the next flush like anyone's. */
+#define PBFT_PROPOSE_LOOPBACK 1u
+typedef int (*pbft_proposer_fn)(void *user, const uint8_t *ops, uint64_t ops_bytes, const uint64_t *op_off,
+                                const uint32_t *op_len, const uint64_t *timestamp, const char *clients, uint64_t view,
+                                uint64_t first_seq, uint64_t n, uint32_t replica, uint8_t *out, size_t cap, size_t *len,
+                                uint8_t *digests, uint8_t *sigs);
+int pbft_replica_propose(pbft_replica *r, uint64_t N, const uint8_t *ops, uint64_t ops_bytes, const uint64_t *op_off,
+                         const uint32_t *op_len, const uint64_t *timestamp, const char *clients, uint32_t flags,
+                         uint8_t *out, size_t cap, size_t *len, uint64_t *first_seq, uint64_t *n_proposed);
+int pbft_replica_set_next_seq(pbft_replica *r, uint64_t seq);
+int pbft_replica_set_proposer(pbft_replica *r, pbft_proposer_fn fn, void *user);
+typedef struct {
+  uint64_t proposed;         /* requests signed and encoded by pbft_replica_propose       */
+  uint64_t calls;            /* pbft_replica_propose calls that proposed requests         */
+  uint64_t held_back;        /* requests offered beyond the window in those calls         */
+  uint64_t loopback_applied; /* own PrePrepares queued by PBFT_PROPOSE_LOOPBACK           */
+  uint64_t propose_ns;       /* host time inside those calls                              */
+} pbft_replica_propose_stats;
+int pbft_replica_get_propose_stats(pbft_replica *r, pbft_replica_propose_stats *out);
+
 /* Non-blocking flush.  _submit: collect every READY sub-window (force = every pending candidate) into one
  * batch and launch it; *n_rows = its signatures (0: nothing launched); PBFT_EBUSY while a batch is in flight.
  * _poll: 1 once no batch is in flight -- the finished batch's accepted votes inserted, the events it

@@ -436,6 +436,71 @@ int pbft_sign_votes_frames_device(pbft_ctx *ctx, const uint8_t *d_env, uint32_t 
 int pbft_sign_votes_frames(pbft_ctx *ctx, const uint8_t *envelopes, uint32_t env_stride, uint64_t N, uint8_t *out,
                            size_t cap, size_t *len, uint64_t *frame_off, uint8_t *sigs);
 
+/* ---- the primary's proposals: client requests in, signed PrePrepare frames out (kernels: pbft_amd/csrc/propose.hip;
+ * frame rule: propose_core.h) ----
+ * What Pbft::add_client_request does with a ClientRequest (src/behavior.rs:63-98): the next sequence number, the
+ * operation's Blake2b-512 digest, the PrePrepare, its multicast.  Request i = operation bytes
+ * [op_off[i], op_off[i] + op_len[i]) of `ops`, timestamp[i] and the client's address in the 64-byte field
+ * clients + 64 * i (up to its first NUL); its sequence number is first_seq + i.  A request is canonical when its
+ * operation has 0 .. PBFT_PP_OP_MAX bytes and its client 1 .. 63, all of them 0x20 .. 0x7E other than '"' and '\': its
+ * frame needs no escaping, is PBFT_PP_FRAME_MIN .. PBFT_PP_FRAME_MAX bytes plus a two-byte varint, and is exactly what
+ * pbft_wire_decode_preprepare (and the device path behind pbft_replica_push_streams) answers with PBFT_PP_OK. */
+#define PBFT_PROPOSE_OK 0      /* canonical: the core's frame                                                       */
+#define PBFT_PROPOSE_GENERAL 1 /* any other request: the frame pbft_wire_encode_frame writes (escapes, long operations,
+                                  an empty or 64-byte client); the device forms write none                          */
+
+/* Host, no context and no GPU: the N signed PrePrepares as consecutive UviBytes frames, for each i byte for byte
+ * pbft_wire_encode_frame of {PrePrepare, view, first_seq + i, digests[i], request i, replica, sigs[i]} -- the analogue of
+ * pbft_wire_encode_votes and the reference form of the functions below.  *len = the stream's full length; returns 0, or
+ * PBFT_EINVAL if cap is too small (then *len still tells the length needed), first_seq + N - 1 wraps, replica > 65535
+ * or an argument is null.  digests and sigs may be NULL for the length query (out = NULL, cap = 0): no frame's length
+ * depends on them.  frame_off [N + 1] (frame i occupies [frame_off[i], frame_off[i + 1])) and status [N]
+ * (PBFT_PROPOSE_*) are optional and complete whatever cap is. */
+int pbft_wire_encode_preprepares(uint64_t N, uint64_t view, uint64_t first_seq, const uint8_t *ops,
+                                 const uint64_t *op_off, const uint32_t *op_len, const uint64_t *timestamp,
+                                 const char *clients /* [N][64] */, uint32_t replica,
+                                 const uint8_t *digests /* [N][64] */, const uint8_t *sigs /* [N][64] */, uint8_t *out,
+                                 size_t cap, size_t *len, uint64_t *frame_off, uint8_t *status);
+
+/* Device form, enqueue only on `stream` (NULL = the context's): three kernel nodes -- the canonical test, the frame
+ * lengths and their scan inside each 64-request tile; the scan over the tiles; one digest and one signature per lane and
+ * the frames -- with no allocation, copy, memset or synchronisation once pbft_propose_reserve(max_n >= N) has sized the
+ * workspace (8 bytes per 64 requests); every loop is bounded; capturable as a plain chain.  The signer is the identity
+ * of pbft_sign_set_seed (PBFT_EINVAL without one), "replica" the index given there.  N <= 2^24.
+ * Per request i, whatever its form: d_digests[i] = Blake2b-512 of the operation where it lies, d_sigs[i] = the RFC 8032
+ * signature over pbft_envelope(0, view, first_seq + i, digest).  A request whose operation does not lie inside
+ * ops_bytes is not read: digest and signature zero, status PBFT_PROPOSE_GENERAL.
+ * A canonical request has status PBFT_PROPOSE_OK and its frame at d_out + d_frame_off[i]; any other has status
+ * PBFT_PROPOSE_GENERAL and frame length 0; d_frame_off[N] is the total.  The frames equal
+ * pbft_wire_encode_preprepares restricted to the OK requests.  When the stream would exceed out_cap, the frames that do
+ * not fit entirely are not written, none is written in part, nothing at or beyond d_out + out_cap is touched, and
+ * d_frame_off, d_digests, d_sigs and d_status are still complete.
+ * d_out may have any alignment; d_ops is 16-byte aligned and nothing outside [d_ops, round_up(ops_bytes, 16)) is read;
+ * d_op_off, d_timestamp, d_frame_off 8-byte aligned, d_op_len, d_digests, d_sigs 4-byte.  PBFT_EINVAL: a null or
+ * misaligned pointer, N > 2^24, first_seq + N - 1 wraps; a refused call has enqueued nothing.  Calls of one context share
+ * the workspace and must be ordered, like its other launches. */
+/* Measuring (pbft_verify_set_option): bytes per store when the wave copies a frame to d_out: 1, 4 (default; 0 restores
+ * it) or 16 (the output's aligned dwords / 16-byte granules with one store each).  The output does not depend on it. */
+#define PBFT_OPT_PROPOSE_WIDTH 22
+int pbft_propose_reserve(pbft_ctx *ctx, uint64_t max_n);
+int pbft_sign_preprepares_frames_device(pbft_ctx *ctx, const uint8_t *d_ops, uint64_t ops_bytes,
+                                        const uint64_t *d_op_off, const uint32_t *d_op_len,
+                                        const uint64_t *d_timestamp, const uint8_t *d_clients, uint64_t view,
+                                        uint64_t first_seq, uint64_t N, uint8_t *d_out, uint64_t out_cap,
+                                        uint64_t *d_frame_off, uint8_t *d_digests, uint8_t *d_sigs, uint8_t *d_status,
+                                        void *stream);
+/* Blocking, host buffers; the complete form: its output equals pbft_wire_encode_preprepares for every input, with the
+ * digests and signatures made on the device.  *len = the bytes needed, computed on the host before anything runs; when
+ * cap is smaller: PBFT_EINVAL, nothing written and nothing launched (out = NULL, cap = 0 asks for the length).  The
+ * device form runs over all N requests; if any status is PBFT_PROPOSE_GENERAL the stream is completed on the host: the
+ * device's frames in order, the others encoded by pbft_wire_encode_frame from the digest and signature that came back.
+ * frame_off [N + 1], digests, sigs [N][64] and status [N] are optional.  PBFT_EINVAL also for an operation outside
+ * ops_bytes; PBFT_EBUSY while an async batch is in flight on the context. */
+int pbft_sign_preprepares_frames(pbft_ctx *ctx, const uint8_t *ops, uint64_t ops_bytes, const uint64_t *op_off,
+                                 const uint32_t *op_len, const uint64_t *timestamp, const char *clients, uint64_t view,
+                                 uint64_t first_seq, uint64_t N, uint8_t *out, size_t cap, size_t *len,
+                                 uint64_t *frame_off, uint8_t *digests, uint8_t *sigs, uint8_t *status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -108,6 +108,27 @@ pub const PBFT_EMIT_LOOPBACK: u32 = 1;
 pub type pbft_signer_fn = Option<unsafe extern "C" fn(user: *mut c_void, envelopes: *const u8, n: u64, replica: u32,
                                                        out: *mut u8, cap: usize, len: *mut usize, sigs: *mut u8)
                                                        -> c_int>;
+/// Counters of the primary's side (pbft_replica_get_propose_stats).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct pbft_replica_propose_stats {
+    pub proposed: u64,
+    pub calls: u64,
+    pub held_back: u64,
+    pub loopback_applied: u64,
+    pub propose_ns: u64,
+}
+pub const PBFT_PROPOSE_LOOPBACK: u32 = 1;
+pub const PBFT_PROPOSE_OK: u8 = 0;
+pub const PBFT_PROPOSE_GENERAL: u8 = 1;
+/// Proposer override of pbft_replica_set_proposer: (user, ops, ops_bytes, op_off, op_len, timestamp, clients, view,
+/// first_seq, n, replica, out, cap, len, digests, sigs).
+pub type pbft_proposer_fn = Option<unsafe extern "C" fn(user: *mut c_void, ops: *const u8, ops_bytes: u64,
+                                                         op_off: *const u64, op_len: *const u32,
+                                                         timestamp: *const u64, clients: *const c_char, view: u64,
+                                                         first_seq: u64, n: u64, replica: u32, out: *mut u8,
+                                                         cap: usize, len: *mut usize, digests: *mut u8,
+                                                         sigs: *mut u8) -> c_int>;
 pub const PBFT_ADMIT_CLEAN: u8 = 0;
 pub const PBFT_ADMIT_CONTESTED: u8 = 1;
 pub const PBFT_ADMIT_REJ_VIEW: u8 = 2;
@@ -519,4 +540,26 @@ extern "C" {
     pub fn pbft_replica_emit_frames(r: *mut pbft_replica, flags: u32, out: *mut u8, cap: usize, len: *mut usize,
                                     n_votes: *mut u64) -> c_int;
     pub fn pbft_replica_get_egress_stats(r: *mut pbft_replica, out: *mut pbft_replica_egress_stats) -> c_int;
+    pub fn pbft_wire_encode_preprepares(n: u64, view: u64, first_seq: u64, ops: *const u8, op_off: *const u64,
+                                        op_len: *const u32, timestamp: *const u64, clients: *const c_char,
+                                        replica: u32, digests: *const u8, sigs: *const u8, out: *mut u8, cap: usize,
+                                        len: *mut usize, frame_off: *mut u64, status: *mut u8) -> c_int;
+    pub fn pbft_propose_reserve(ctx: *mut pbft_ctx, max_n: u64) -> c_int;
+    pub fn pbft_sign_preprepares_frames_device(ctx: *mut pbft_ctx, d_ops: *const u8, ops_bytes: u64,
+                                               d_op_off: *const u64, d_op_len: *const u32, d_timestamp: *const u64,
+                                               d_clients: *const u8, view: u64, first_seq: u64, n: u64,
+                                               d_out: *mut u8, out_cap: u64, d_frame_off: *mut u64,
+                                               d_digests: *mut u8, d_sigs: *mut u8, d_status: *mut u8,
+                                               stream: *mut c_void) -> c_int;
+    pub fn pbft_sign_preprepares_frames(ctx: *mut pbft_ctx, ops: *const u8, ops_bytes: u64, op_off: *const u64,
+                                        op_len: *const u32, timestamp: *const u64, clients: *const c_char, view: u64,
+                                        first_seq: u64, n: u64, out: *mut u8, cap: usize, len: *mut usize,
+                                        frame_off: *mut u64, digests: *mut u8, sigs: *mut u8, status: *mut u8) -> c_int;
+    pub fn pbft_replica_propose(r: *mut pbft_replica, n: u64, ops: *const u8, ops_bytes: u64, op_off: *const u64,
+                                op_len: *const u32, timestamp: *const u64, clients: *const c_char, flags: u32,
+                                out: *mut u8, cap: usize, len: *mut usize, first_seq: *mut u64,
+                                n_proposed: *mut u64) -> c_int;
+    pub fn pbft_replica_set_next_seq(r: *mut pbft_replica, seq: u64) -> c_int;
+    pub fn pbft_replica_set_proposer(r: *mut pbft_replica, f: pbft_proposer_fn, user: *mut c_void) -> c_int;
+    pub fn pbft_replica_get_propose_stats(r: *mut pbft_replica, out: *mut pbft_replica_propose_stats) -> c_int;
 }

@@ -23,7 +23,7 @@
 use std::ffi::CStr;
 use std::fmt;
 use std::marker::PhantomData;
-use std::os::raw::{c_int, c_void};
+use std::os::raw::{c_char, c_int, c_void};
 use std::ptr;
 
 pub mod ffi;
@@ -514,8 +514,86 @@ impl GpuVerifier {
         out.truncate(len);
         Ok((out, off, sigs))
     }
+    /// The primary's side of a round (pbft_sign_preprepares_frames): the requests hashed, their PrePrepares with
+    /// sequence numbers first_seq, first_seq + 1, ... signed with the installed seed and written as UviBytes/JSON
+    /// frames; requests that are not of the canonical form are completed on the host.
+    pub fn sign_preprepares_frames(&mut self, view: u64, first_seq: u64, requests: &[ClientRequest]) -> Result<Proposal> {
+        let p = PackedRequests::new(requests);
+        let n = requests.len();
+        let mut len = 0usize;
+        unsafe {
+            // the size query: PBFT_EINVAL with the length needed, unless there is nothing to write
+            ffi::pbft_sign_preprepares_frames(self.ctx, p.ops.as_ptr(), p.ops_bytes, p.off.as_ptr(), p.len.as_ptr(),
+                                              p.ts.as_ptr(), p.clients.as_ptr() as *const c_char, view, first_seq,
+                                              n as u64, ptr::null_mut(), 0, &mut len, ptr::null_mut(), ptr::null_mut(),
+                                              ptr::null_mut(), ptr::null_mut());
+        }
+        let mut out = Proposal { stream: vec![0u8; len], frame_off: vec![0u64; n + 1], digests: vec![[0u8; 64]; n],
+                                 sigs: vec![[0u8; 64]; n], status: vec![0u8; n] };
+        check(unsafe {
+            ffi::pbft_sign_preprepares_frames(self.ctx, p.ops.as_ptr(), p.ops_bytes, p.off.as_ptr(), p.len.as_ptr(),
+                                              p.ts.as_ptr(), p.clients.as_ptr() as *const c_char, view, first_seq,
+                                              n as u64, out.stream.as_mut_ptr(), out.stream.len(), &mut len,
+                                              out.frame_off.as_mut_ptr(), out.digests.as_mut_ptr() as *mut u8,
+                                              out.sigs.as_mut_ptr() as *mut u8, out.status.as_mut_ptr())
+        })?;
+        out.stream.truncate(len);
+        Ok(out)
+    }
     pub fn raw(&self) -> *mut ffi::pbft_ctx {
         self.ctx
+    }
+}
+
+/// One client request as the primary receives it (the reference's ClientRequest, src/message.rs:174-179).
+#[derive(Clone, Copy, Debug)]
+pub struct ClientRequest<'a> {
+    pub operation: &'a [u8],
+    pub timestamp: u64,
+    /// The client's address as serde writes it ("127.0.0.1:8080"); at most 64 bytes are used.
+    pub client: &'a str,
+}
+
+/// What sign_preprepares_frames returns: the frames, frame i at [frame_off[i], frame_off[i + 1]), and per request the
+/// operation's Blake2b-512 digest, R || S over the PrePrepare's envelope and PBFT_PROPOSE_OK / _GENERAL.
+#[derive(Clone, Debug, Default)]
+pub struct Proposal {
+    pub stream: Vec<u8>,
+    pub frame_off: Vec<u64>,
+    pub digests: Vec<[u8; 64]>,
+    pub sigs: Vec<[u8; 64]>,
+    pub status: Vec<u8>,
+}
+
+// The arrays the proposal entry points take: operations back to back (padded to 16 bytes), 64-byte client fields.
+struct PackedRequests {
+    ops: Vec<u8>,
+    ops_bytes: u64,
+    off: Vec<u64>,
+    len: Vec<u32>,
+    ts: Vec<u64>,
+    clients: Vec<[u8; 64]>,
+}
+
+impl PackedRequests {
+    fn new(requests: &[ClientRequest]) -> Self {
+        let mut p = PackedRequests { ops: Vec::new(), ops_bytes: 0, off: Vec::new(), len: Vec::new(), ts: Vec::new(),
+                                     clients: Vec::new() };
+        for r in requests {
+            p.off.push(p.ops.len() as u64);
+            p.len.push(r.operation.len() as u32);
+            p.ops.extend_from_slice(r.operation);
+            p.ts.push(r.timestamp);
+            let mut c = [0u8; 64];
+            let b = r.client.as_bytes();
+            let k = b.len().min(64);
+            c[..k].copy_from_slice(&b[..k]);
+            p.clients.push(c);
+        }
+        p.ops_bytes = p.ops.len() as u64;
+        let padded = (p.ops.len() + 16) / 16 * 16;
+        p.ops.resize(padded, 0);
+        p
     }
 }
 
@@ -893,6 +971,39 @@ impl<'a> Replica<'a> {
             out.truncate(len);
         }
         Ok((out, votes))
+    }
+    /// The primary's add_client_request for a batch (pbft_replica_propose): the requests that fit the window get the
+    /// next sequence numbers and come back as signed PrePrepare frames, the bytes to write to every connected peer.
+    /// Returns (frames, first sequence number, requests proposed); the rest are the caller's to offer again.
+    /// `loopback`: each PrePrepare is also applied as this replica's own (verified in the next flush).
+    pub fn propose(&mut self, requests: &[ClientRequest], loopback: bool) -> Result<(Vec<u8>, u64, u64)> {
+        let flags = if loopback { ffi::PBFT_PROPOSE_LOOPBACK } else { 0 };
+        let p = PackedRequests::new(requests);
+        let (mut len, mut first, mut n) = (0usize, 0u64, 0u64);
+        check(unsafe {
+            ffi::pbft_replica_propose(self.raw, requests.len() as u64, p.ops.as_ptr(), p.ops_bytes, p.off.as_ptr(),
+                                      p.len.as_ptr(), p.ts.as_ptr(), p.clients.as_ptr() as *const c_char, 0,
+                                      ptr::null_mut(), 0, &mut len, &mut first, &mut n)
+        })?;
+        let mut out = vec![0u8; len];
+        if len > 0 {
+            check(unsafe {
+                ffi::pbft_replica_propose(self.raw, requests.len() as u64, p.ops.as_ptr(), p.ops_bytes, p.off.as_ptr(),
+                                          p.len.as_ptr(), p.ts.as_ptr(), p.clients.as_ptr() as *const c_char, flags,
+                                          out.as_mut_ptr(), out.len(), &mut len, &mut first, &mut n)
+            })?;
+            out.truncate(len);
+        }
+        Ok((out, first, n))
+    }
+    /// The next sequence number a proposal gets (pbft_replica_set_next_seq; 1 at creation).
+    pub fn set_next_seq(&mut self, seq: u64) -> Result<()> {
+        check(unsafe { ffi::pbft_replica_set_next_seq(self.raw, seq) }).map(|_| ())
+    }
+    pub fn propose_stats(&self) -> ffi::pbft_replica_propose_stats {
+        let mut s = ffi::pbft_replica_propose_stats::default();
+        unsafe { ffi::pbft_replica_get_propose_stats(self.raw, &mut s) };
+        s
     }
     pub fn egress_stats(&self) -> ffi::pbft_replica_egress_stats {
         let mut s = ffi::pbft_replica_egress_stats::default();

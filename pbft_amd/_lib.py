@@ -34,6 +34,9 @@ EXPORTS = (
     "pbft_verify_streams_admit_pp", "pbft_egress_reserve", "pbft_sign_votes_frames_device", "pbft_sign_votes_frames",
     # include/pbft_verify.h, egress
     "pbft_sign_set_seed",
+    # include/pbft_wire.h, the primary's proposals
+    "pbft_wire_encode_preprepares", "pbft_propose_reserve", "pbft_sign_preprepares_frames_device",
+    "pbft_sign_preprepares_frames",
 )
 
 ERRORS = {0: "PBFT_OK", -1: "PBFT_EINVAL", -2: "PBFT_EHIP", -3: "PBFT_ENOKEYS",
@@ -152,6 +155,13 @@ def load() -> ctypes.CDLL:
         "pbft_egress_reserve": (i32, [vp, u64]),
         "pbft_sign_votes_frames_device": (i32, [vp, vp, u32, u64, vp, u64, vp, vp, vp]),
         "pbft_sign_votes_frames": (i32, [vp, vp, u32, u64, vp, ctypes.c_size_t, vp, vp, vp]),
+        "pbft_wire_encode_preprepares": (i32, [u64, u64, u64, vp, vp, vp, vp, vp, u32, vp, vp, vp, ctypes.c_size_t, vp,
+                                               vp, vp]),
+        "pbft_propose_reserve": (i32, [vp, u64]),
+        "pbft_sign_preprepares_frames_device": (i32, [vp, vp, u64, vp, vp, vp, vp, u64, u64, u64, vp, u64, vp, vp, vp,
+                                                      vp, vp]),
+        "pbft_sign_preprepares_frames": (i32, [vp, vp, u64, vp, vp, vp, vp, u64, u64, u64, vp, ctypes.c_size_t, vp, vp,
+                                               vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -62,6 +62,9 @@
 #pragma weak pbft_sign_set_seed
 #pragma weak pbft_sign_votes_frames
 #pragma weak pbft_sign_batch
+// ... and of the primary's PrePrepares (propose.hip): without it only a proposer override (pbft_replica_set_proposer)
+// proposes.
+#pragma weak pbft_sign_preprepares_frames
 
 namespace {
 
@@ -551,6 +554,12 @@ struct pbft_replica {
   std::vector<uint8_t> outbox;
   std::vector<uint8_t> out_sigs;  // pbft_replica_emit_frames: the signatures of the call (loopback)
   pbft_replica_egress_stats estats{};
+  // the primary's side (pbft_replica_propose)
+  uint64_t next_seq = 1;  // PrePrepareSequence starts at 0 and increments before use (src/message.rs:154-172)
+  pbft_proposer_fn proposer_fn = nullptr;
+  void* proposer_user = nullptr;
+  std::vector<uint8_t> prop_digests, prop_sigs;  // of the call (loopback)
+  pbft_replica_propose_stats pstats{};
 };
 
 static uint32_t primary_of(const pbft_replica* r, uint64_t view) { return (uint32_t)(view % r->n); }
@@ -3211,6 +3220,91 @@ int pbft_replica_get_egress_stats(pbft_replica* r, pbft_replica_egress_stats* ou
   if (!r || !out) return PBFT_EINVAL;
   *out = r->estats;
   out->queued = r->outbox.size() / PBFT_ENVELOPE_BYTES;
+  return PBFT_OK;
+}
+
+// ---- the primary's side: client requests in, signed PrePrepare frames out (include/pbft_replica.h) ----
+int pbft_replica_set_next_seq(pbft_replica* r, uint64_t seq) {
+  if (!r) return PBFT_EINVAL;
+  r->next_seq = seq;
+  return PBFT_OK;
+}
+
+int pbft_replica_set_proposer(pbft_replica* r, pbft_proposer_fn fn, void* user) {
+  if (!r) return PBFT_EINVAL;
+  r->proposer_fn = fn;
+  r->proposer_user = fn ? user : nullptr;
+  return PBFT_OK;
+}
+
+int pbft_replica_propose(pbft_replica* r, uint64_t N, const uint8_t* ops, uint64_t ops_bytes, const uint64_t* op_off,
+                         const uint32_t* op_len, const uint64_t* timestamp, const char* clients, uint32_t flags,
+                         uint8_t* out, size_t cap, size_t* len, uint64_t* first_seq, uint64_t* n_proposed) {
+  if (!r || (flags & ~PBFT_PROPOSE_LOOPBACK) || (cap && !out) || (ops_bytes && !ops) ||
+      (N && (!op_off || !op_len || !timestamp || !clients)))
+    return PBFT_EINVAL;
+  if (len) *len = 0;
+  if (first_seq) *first_seq = 0;
+  if (n_proposed) *n_proposed = 0;
+  const uint64_t view = r->current_view;
+  if (primary_of(r, view) != r->self) return PBFT_EINVAL;  // only the view's primary assigns sequence numbers
+  for (uint64_t i = 0; i < N; ++i)
+    if (op_len[i] > ops_bytes || op_off[i] > ops_bytes - op_len[i]) return PBFT_EINVAL;
+  const auto t0 = std::chrono::steady_clock::now();
+  // the requests whose sequence number lies inside the window (a number that wraps to 0 is never inside)
+  const uint64_t start = r->next_seq > r->h ? r->next_seq : r->h + 1;
+  uint64_t n = 0;
+  while (n < N && in_log(r, start + n)) ++n;
+  size_t need = 0;
+  if (n && pbft_wire_encode_preprepares(n, view, start, ops, op_off, op_len, timestamp, clients, r->self, nullptr,
+                                        nullptr, nullptr, 0, &need, nullptr, nullptr) != 0)
+    return PBFT_EINVAL;
+  if (len) *len = need;
+  if (first_seq) *first_seq = start;
+  if (n_proposed) *n_proposed = n;
+  if (!out && cap == 0) return PBFT_OK;  // the size query
+  if (cap < need) return PBFT_EINVAL;
+  if (n == 0) {
+    r->pstats.held_back += N;  // (the window is full: nothing to sign)
+    return PBFT_OK;
+  }
+  r->prop_digests.resize(64 * (size_t)n);
+  r->prop_sigs.resize(64 * (size_t)n);
+  size_t got = 0;
+  int rc;
+  if (r->proposer_fn) {
+    rc = r->proposer_fn(r->proposer_user, ops, ops_bytes, op_off, op_len, timestamp, clients, view, start, n, r->self,
+                        out, cap, &got, r->prop_digests.data(), r->prop_sigs.data());
+  } else {
+    if (!r->seed_set || !r->dctx) rc = PBFT_EINVAL;  // no signer (pbft_replica_set_signing_seed)
+    else if (!pbft_sign_preprepares_frames) rc = PBFT_ENODEV;
+    else
+      rc = pbft_sign_preprepares_frames(r->dctx, ops, ops_bytes, op_off, op_len, timestamp, clients, view, start, n, out,
+                                        cap, &got, nullptr, r->prop_digests.data(), r->prop_sigs.data(), nullptr);
+  }
+  if (rc == PBFT_OK && got != need) rc = PBFT_EINVAL;  // (not the frames of these requests)
+  if (rc != PBFT_OK) {
+    if (len) *len = 0;
+    if (n_proposed) *n_proposed = 0;
+    return rc;
+  }
+  r->next_seq = start + n;  // (wraps to 0 behind 2^64 - 1: h + 1 then rules)
+  if (flags & PBFT_PROPOSE_LOOPBACK) {
+    for (uint64_t i = 0; i < n; ++i) {
+      const uint8_t* d = r->prop_digests.data() + 64 * i;
+      if (pre_prepare_apply(r, view, start + i, d, d, r->prop_sigs.data() + 64 * i) == 1) ++r->pstats.loopback_applied;
+    }
+  }
+  r->pstats.proposed += n;
+  r->pstats.held_back += N - n;
+  ++r->pstats.calls;
+  r->pstats.propose_ns += ns_since(t0);
+  return PBFT_OK;
+}
+
+int pbft_replica_get_propose_stats(pbft_replica* r, pbft_replica_propose_stats* out) {
+  if (!r || !out) return PBFT_EINVAL;
+  *out = r->pstats;
   return PBFT_OK;
 }
 

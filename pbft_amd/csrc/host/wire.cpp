@@ -19,6 +19,7 @@
 #endif
 
 #include "../../../include/pbft_replica.h"
+#include "../propose_core.h"
 
 namespace {
 
@@ -711,6 +712,72 @@ int pbft_wire_encode_votes(uint64_t N, const uint8_t* kind, const uint64_t* view
   }
   *len = off;
   return rc;
+}
+
+// The primary's side of pbft_wire_encode_votes.  A canonical request's frame comes from propose_core.h's writer (the
+// one the device runs), every other one from pbft_wire_encode_frame.
+int pbft_wire_encode_preprepares(uint64_t N, uint64_t view, uint64_t first_seq, const uint8_t* ops,
+                                 const uint64_t* op_off, const uint32_t* op_len, const uint64_t* timestamp,
+                                 const char* clients, uint32_t replica, const uint8_t* digests, const uint8_t* sigs,
+                                 uint8_t* out, size_t cap, size_t* len, uint64_t* frame_off, uint8_t* status) {
+  if (!len) return PBFT_EINVAL;
+  *len = 0;
+  if ((!out && cap) || replica > pbft::PR_MAX_REPLICA) return PBFT_EINVAL;
+  if (N && (!op_off || !op_len || !timestamp || !clients || first_seq + (N - 1) < first_seq)) return PBFT_EINVAL;
+  const bool query = !out && cap == 0;
+  if (N && !query && (!digests || !sigs)) return PBFT_EINVAL;
+  static const uint8_t zero[64] = {0};
+  size_t off = 0;
+  int rc = 0;
+  for (uint64_t i = 0; i < N; ++i) {
+    const uint8_t* op = ops ? ops + op_off[i] : nullptr;
+    if (!op && op_len[i]) return PBFT_EINVAL;
+    const uint8_t* cl = (const uint8_t*)clients + pbft::PR_CLIENT_FIELD * i;
+    const uint32_t cl_len = pbft::pr_client_len(cl);
+    const uint8_t* dg = digests ? digests + 64 * i : zero;
+    const uint8_t* sg = sigs ? sigs + 64 * i : zero;
+    const uint64_t seq = first_seq + i;
+    if (frame_off) frame_off[i] = off;
+    size_t fl = 0;
+    if (pbft::pr_canonical(op, op_len[i], cl, cl_len)) {
+      if (status) status[i] = PBFT_PROPOSE_OK;
+      fl = pbft::pr_frame_len(view, seq, timestamp[i], replica, op_len[i], cl_len);
+      if (out && off <= cap && cap - off >= fl) {
+        uint32_t dw[16], sw[16];
+        memcpy(dw, dg, 64);
+        memcpy(sw, sg, 64);
+        uint8_t* dst = out + off;
+        auto put = [dst](uint32_t pos, uint8_t b) { dst[pos] = b; };
+        pbft::pr_write_frame(put, view, seq, dw, op, op_len[i], timestamp[i], cl, cl_len, replica, sw);
+      } else {
+        rc = PBFT_EINVAL;  // (no room: keep counting the length)
+      }
+    } else {
+      if (status) status[i] = PBFT_PROPOSE_GENERAL;
+      pbft_wire_msg m;
+      memset(&m, 0, sizeof m);
+      m.kind = PBFT_MSG_PREPREPARE;
+      m.view = view;
+      m.seq = seq;
+      memcpy(m.digest, dg, 64);
+      m.digest_ok = 1;
+      m.has_sig = 1;
+      m.replica = replica;
+      memcpy(m.sig, sg, 64);
+      m.operation = (const char*)op;
+      m.operation_len = op_len[i];
+      m.timestamp = timestamp[i];
+      memcpy(m.client, cl, sizeof m.client);
+      const bool room = out && off <= cap;
+      const int e = pbft_wire_encode_frame(&m, room ? out + off : nullptr, room ? cap - off : 0, &fl);
+      if (fl == 0) return PBFT_EINVAL;
+      if (e) rc = PBFT_EINVAL;
+    }
+    off += fl;
+  }
+  if (frame_off) frame_off[N] = off;
+  *len = off;
+  return query ? 0 : rc;
 }
 
 int pbft_records_pack(const uint8_t* R, const uint8_t* S, const uint16_t* key_idx, const uint8_t* msg,

@@ -41,6 +41,7 @@ using namespace pbft;
 #include "wire_index_kernels.h"
 #include "wire_pp_kernels.h"
 #include "egress_kernels.h"
+#include "propose_kernels.h"
 // Finish configuration by batch size (signatures per lane, product tree, waves per SIMD), measured on MI355X
 // with the lane-parallel wave inversion (profiles/r03/ab_finish.txt): 131k 0.2115 -> 0.1906 ms (width 2),
 // 262k 0.3628 -> 0.3429 (width 4), 2^20 finish kernel 118.6 -> 91.4 us (width 8, tree, 2 waves per SIMD).
@@ -273,6 +274,13 @@ struct pbft_ctx {
   size_t egress_io_cap = 0;  // bytes
   int egress_block = 64;
   bool egress_direct = false;
+  // pbft_sign_preprepares_frames_device: the tile sums (grow-only; pbft_propose_reserve); the blocking form's requests,
+  // outputs and frames (grow-only)
+  uint8_t* d_propose = nullptr;
+  size_t propose_cap = 0;  // bytes
+  uint8_t* d_propose_io = nullptr;
+  size_t propose_io_cap = 0;  // bytes
+  int propose_width = PROPOSE_WIDTH_DEFAULT;
 };
 
 #ifndef PBFT_ENV_SCHED
@@ -1061,6 +1069,8 @@ int pbft_verify_ctx_destroy(pbft_ctx* c) {
   }
   (void)hipFree(c->d_egress);
   (void)hipFree(c->d_egress_io);
+  (void)hipFree(c->d_propose);
+  (void)hipFree(c->d_propose_io);
   if (c->h_bitmap) (void)hipHostFree(c->h_bitmap);
   if (c->h_stage) (void)hipHostFree(c->h_stage);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -3032,6 +3042,141 @@ int pbft_sign_votes_frames(pbft_ctx* c, const uint8_t* envelopes, uint32_t env_s
   return PBFT_OK;
 }
 
+// ---- the primary's proposals: requests hashed, PrePrepares signed and framed on the device (include/pbft_wire.h;
+// propose.hip) ----
+static int ensure_propose(pbft_ctx* c, uint64_t N) {
+  const size_t bytes = propose_ws_bytes(N ? N : 1);
+  if (bytes <= c->propose_cap) return PBFT_OK;
+  if (c->d_propose) HIP_TRY(hipFree(c->d_propose));  // (waits for the device: an earlier call may still use it)
+  c->d_propose = nullptr;
+  c->propose_cap = 0;
+  if (hipMalloc(&c->d_propose, bytes) != hipSuccess) return set_err(PBFT_ENOMEM, "propose workspace alloc");
+  c->propose_cap = bytes;
+  return PBFT_OK;
+}
+
+int pbft_propose_reserve(pbft_ctx* c, uint64_t max_n) {
+  if (!c) return set_err(PBFT_EINVAL, "null context");
+  if (max_n > pbft::PR_MAX_N) return set_err(PBFT_EINVAL, "more than 2^24 requests to propose");
+  HIP_TRY(hipSetDevice(c->device));
+  return ensure_propose(c, max_n);
+}
+
+int pbft_sign_preprepares_frames_device(pbft_ctx* c, const uint8_t* d_ops, uint64_t ops_bytes, const uint64_t* d_op_off,
+                                        const uint32_t* d_op_len, const uint64_t* d_timestamp, const uint8_t* d_clients,
+                                        uint64_t view, uint64_t first_seq, uint64_t N, uint8_t* d_out, uint64_t out_cap,
+                                        uint64_t* d_frame_off, uint8_t* d_digests, uint8_t* d_sigs, uint8_t* d_status,
+                                        void* stream) {
+  if (!c) return set_err(PBFT_EINVAL, "null context");
+  if (!c->sign_set) return set_err(PBFT_EINVAL, "no signing seed (pbft_sign_set_seed)");
+  if (N > pbft::PR_MAX_N) return set_err(PBFT_EINVAL, "more than 2^24 requests to propose");
+  if (N && first_seq + (N - 1) < first_seq) return set_err(PBFT_EINVAL, "sequence numbers wrap");
+  if (!d_frame_off || (ops_bytes && !d_ops) || (out_cap && !d_out) ||
+      (N && (!d_op_off || !d_op_len || !d_timestamp || !d_clients || !d_digests || !d_sigs || !d_status)))
+    return set_err(PBFT_EINVAL, "bad propose argument");
+  if (((uintptr_t)d_ops & 15) || ((uintptr_t)d_op_off & 7) || ((uintptr_t)d_op_len & 3) || ((uintptr_t)d_timestamp & 7) ||
+      ((uintptr_t)d_frame_off & 7) || ((uintptr_t)d_digests & 3) || ((uintptr_t)d_sigs & 3))
+    return set_err(PBFT_EINVAL, "misaligned propose pointer");
+  HIP_TRY(hipSetDevice(c->device));
+  int rc = ensure_propose(c, N);
+  if (rc) return rc;
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  HIP_TRY(launch_propose(d_ops, ops_bytes, d_op_off, d_op_len, d_timestamp, d_clients, view, first_seq, N,
+                         c->d_sign_key, c->d_tabB, (uint64_t*)c->d_propose, d_out, out_cap, d_frame_off, d_digests,
+                         d_sigs, d_status, c->propose_width, st));
+  return PBFT_OK;
+}
+
+int pbft_sign_preprepares_frames(pbft_ctx* c, const uint8_t* ops, uint64_t ops_bytes, const uint64_t* op_off,
+                                 const uint32_t* op_len, const uint64_t* timestamp, const char* clients, uint64_t view,
+                                 uint64_t first_seq, uint64_t N, uint8_t* out, size_t cap, size_t* len,
+                                 uint64_t* frame_off, uint8_t* digests, uint8_t* sigs, uint8_t* status) {
+  if (!c || !len) return set_err(PBFT_EINVAL, "null propose argument");
+  *len = 0;
+  if (!c->sign_set) return set_err(PBFT_EINVAL, "no signing seed (pbft_sign_set_seed)");
+  if (N > pbft::PR_MAX_N) return set_err(PBFT_EINVAL, "more than 2^24 requests to propose");
+  if ((N && (!op_off || !op_len || !timestamp || !clients)) || (ops_bytes && !ops) || (cap && !out))
+    return set_err(PBFT_EINVAL, "bad propose argument");
+  if (N && first_seq + (N - 1) < first_seq) return set_err(PBFT_EINVAL, "sequence numbers wrap");
+  if (c->in_flight) return set_err(PBFT_EBUSY, "async batch in flight");
+  for (uint64_t i = 0; i < N; ++i)
+    if (op_len[i] > ops_bytes || op_off[i] > ops_bytes - op_len[i])
+      return set_err(PBFT_EINVAL, "an operation outside ops_bytes");
+  // the layout is a function of the requests and the replica index: known before anything runs
+  std::vector<uint64_t> h_off(N + 1);
+  std::vector<uint8_t> h_st(N ? N : 1);
+  size_t need = 0;
+  int rc = pbft_wire_encode_preprepares(N, view, first_seq, ops, op_off, op_len, timestamp, clients, c->sign_replica,
+                                        nullptr, nullptr, nullptr, 0, &need, h_off.data(), h_st.data());
+  if (rc) return set_err(PBFT_EINVAL, "bad propose argument");
+  *len = need;
+  if (need > cap) return set_err(PBFT_EINVAL, "output buffer too small for the frames");
+  if (frame_off) memcpy(frame_off, h_off.data(), 8 * (size_t)(N + 1));
+  if (N == 0) return PBFT_OK;
+  uint64_t n_general = 0;
+  size_t dev_bytes = 0;  // the canonical requests' frames: what the device writes
+  for (uint64_t i = 0; i < N; ++i) {
+    if (h_st[i] == PBFT_PROPOSE_GENERAL) ++n_general;
+    else dev_bytes += (size_t)(h_off[i + 1] - h_off[i]);
+  }
+  if (status) memcpy(status, h_st.data(), N);
+  HIP_TRY(hipSetDevice(c->device));
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t oOff = up(ops_bytes + 16), oLen = oOff + up(8 * (size_t)N), oTs = oLen + up(4 * (size_t)N),
+               oCl = oTs + up(8 * (size_t)N), oF = oCl + up(64 * (size_t)N), oD = oF + up(8 * (size_t)(N + 1)),
+               oS = oD + up(64 * (size_t)N), oSt = oS + up(64 * (size_t)N), oO = oSt + up(N);
+  const size_t total = oO + up(dev_bytes);
+  if (total > c->propose_io_cap) {
+    if (c->d_propose_io) HIP_TRY(hipFree(c->d_propose_io));
+    c->d_propose_io = nullptr;
+    c->propose_io_cap = 0;
+    if (hipMalloc(&c->d_propose_io, total) != hipSuccess) return set_err(PBFT_ENOMEM, "propose buffers alloc");
+    c->propose_io_cap = total;
+  }
+  rc = ensure_propose(c, N);
+  if (rc) return rc;
+  uint8_t* d = c->d_propose_io;
+  if (ops_bytes) HIP_TRY(hipMemcpyAsync(d, ops, ops_bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(d + oOff, op_off, 8 * (size_t)N, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(d + oLen, op_len, 4 * (size_t)N, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(d + oTs, timestamp, 8 * (size_t)N, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(d + oCl, clients, 64 * (size_t)N, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(launch_propose(d, ops_bytes, (const uint64_t*)(d + oOff), (const uint32_t*)(d + oLen),
+                         (const uint64_t*)(d + oTs), d + oCl, view, first_seq, N, c->d_sign_key, c->d_tabB,
+                         (uint64_t*)c->d_propose, d + oO, dev_bytes, (uint64_t*)(d + oF), d + oD, d + oS, d + oSt,
+                         c->propose_width, c->stream));
+  std::vector<uint8_t> tmp_frames, tmp_d, tmp_s;
+  uint8_t* frames_to = out;  // all canonical: the device's stream is the answer
+  if (n_general) {
+    tmp_frames.resize(dev_bytes ? dev_bytes : 1);
+    frames_to = tmp_frames.data();
+    if (!digests) { tmp_d.resize(64 * (size_t)N); digests = tmp_d.data(); }
+    if (!sigs) { tmp_s.resize(64 * (size_t)N); sigs = tmp_s.data(); }
+  }
+  if (dev_bytes) HIP_TRY(hipMemcpyAsync(frames_to, d + oO, dev_bytes, hipMemcpyDeviceToHost, c->stream));
+  if (digests) HIP_TRY(hipMemcpyAsync(digests, d + oD, 64 * (size_t)N, hipMemcpyDeviceToHost, c->stream));
+  if (sigs) HIP_TRY(hipMemcpyAsync(sigs, d + oS, 64 * (size_t)N, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (n_general) {  // the complete stream, on the host: the device's frames in order, the others from the general encoder
+    size_t from = 0;
+    for (uint64_t i = 0; i < N; ++i) {
+      const size_t at = (size_t)h_off[i], fl = (size_t)(h_off[i + 1] - h_off[i]);
+      if (h_st[i] == PBFT_PROPOSE_OK) {
+        memcpy(out + at, tmp_frames.data() + from, fl);
+        from += fl;
+        continue;
+      }
+      size_t got = 0;
+      const uint64_t off1 = 0;
+      rc = pbft_wire_encode_preprepares(1, view, first_seq + i, ops + op_off[i], &off1, op_len + i, timestamp + i,
+                                        clients + 64 * i, c->sign_replica, digests + 64 * i, sigs + 64 * i, out + at, fl,
+                                        &got, nullptr, nullptr);
+      if (rc || got != fl) return set_err(PBFT_EINVAL, "general frame encode");
+    }
+  }
+  return PBFT_OK;
+}
+
 int pbft_verify_reserve(pbft_ctx* c, uint64_t max_n) {
   if (!c) return set_err(PBFT_EINVAL, "null context");
   HIP_TRY(hipSetDevice(c->device));
@@ -3084,6 +3229,10 @@ int pbft_verify_set_option(pbft_ctx* c, int option, uint64_t value) {
     case PBFT_OPT_EGRESS_DIRECT:
       if (value > 1) return set_err(PBFT_EINVAL, "egress direct is 0 or 1");
       c->egress_direct = value == 1;
+      return PBFT_OK;
+    case PBFT_OPT_PROPOSE_WIDTH:
+      if (value != 0 && value != 1 && value != 4 && value != 16) return set_err(PBFT_EINVAL, "propose width is 1, 4 or 16");
+      c->propose_width = value ? (int)value : PROPOSE_WIDTH_DEFAULT;
       return PBFT_OK;
   }
   return set_err(PBFT_EINVAL, "unknown option");

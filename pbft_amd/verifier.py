@@ -626,6 +626,7 @@ class GpuBatchVerifier:
 
     OPT_INDEX_TILE = 19
     OPT_EGRESS_BLOCK, OPT_EGRESS_DIRECT = 20, 21
+    OPT_PROPOSE_WIDTH = 22
     OPT_GROUP_SEED, OPT_GROUP_HASH_BITS = 16, 17
     OPT_SPLIT_BELOW, OPT_FINISH_WIDTH, OPT_KEY_TABLE_BUDGET_MB, OPT_FINISH_TREE, OPT_LAT_SPLIT = 1, 2, 3, 4, 5
     OPT_KERNEL_TIMING = 7
@@ -722,6 +723,43 @@ class GpuBatchVerifier:
         d_sigs [n][64]."""
         check(self._lib.pbft_sign_votes_frames_device(self._ctx, d_env or None, env_stride, n, d_out or None, out_cap,
                                                       d_frame_off or None, d_sigs or None, stream or None))
+
+    # -- the primary's proposals: client requests hashed, signed and framed on the GPU (include/pbft_wire.h) ------
+    def propose_reserve(self, max_n: int) -> None:
+        """pbft_propose_reserve: pre-size the proposal workspace (required before capturing
+        sign_preprepares_frames_device into a graph)."""
+        check(self._lib.pbft_propose_reserve(self._ctx, max_n))
+
+    def sign_preprepares_frames(self, view: int, first_seq: int, requests):
+        """pbft_sign_preprepares_frames: `requests` (wire.pack_requests' tuple, host) -> (stream, frame_off [N + 1],
+        digests [N][64], sigs [N][64], status [N]): the signed PrePrepares' UviBytes frames, what
+        wire.encode_preprepares writes for them, under the identity of set_signing_seed."""
+        data, ops_bytes, offs, lens, ts, cl = requests
+        n = len(lens)
+        need = ctypes.c_size_t()
+        args = (self._ctx, _ptr(data), ops_bytes, _ptr(offs), _ptr(lens), _ptr(ts), _ptr(cl), view, first_seq, n)
+        rc = self._lib.pbft_sign_preprepares_frames(*args, None, 0, ctypes.byref(need), None, None, None, None)
+        if rc and not need.value:
+            check(rc)
+        out = np.zeros(max(need.value, 1), dtype=np.uint8)
+        off = np.zeros(n + 1, dtype=np.uint64)
+        dig, sigs = np.zeros((n, 64), dtype=np.uint8), np.zeros((n, 64), dtype=np.uint8)
+        st = np.zeros(max(n, 1), dtype=np.uint8)
+        check(self._lib.pbft_sign_preprepares_frames(*args, _ptr(out), need.value, ctypes.byref(need), _ptr(off),
+                                                     _ptr(dig) if n else None, _ptr(sigs) if n else None, _ptr(st)))
+        return out[:need.value], off, dig, sigs, st[:n]
+
+    def sign_preprepares_frames_device(self, d_ops: int, ops_bytes: int, d_op_off: int, d_op_len: int, d_timestamp: int,
+                                       d_clients: int, view: int, first_seq: int, n: int, d_out: int, out_cap: int,
+                                       d_frame_off: int, d_digests: int, d_sigs: int, d_status: int,
+                                       stream: int = 0) -> None:
+        """pbft_sign_preprepares_frames_device: enqueue only (raw device pointers): n requests -> the canonical ones'
+        frames at d_out (any alignment, at most out_cap bytes, whole frames only), d_frame_off [n + 1] u64, d_digests
+        and d_sigs [n][64], d_status [n]."""
+        check(self._lib.pbft_sign_preprepares_frames_device(
+            self._ctx, d_ops or None, ops_bytes, d_op_off or None, d_op_len or None, d_timestamp or None,
+            d_clients or None, view, first_seq, n, d_out or None, out_cap, d_frame_off or None, d_digests or None,
+            d_sigs or None, d_status or None, stream or None))
 
     def close(self):
         if self._ctx:

@@ -205,3 +205,46 @@ def encode_votes(kind, view, seq, digests, replica, sigs) -> np.ndarray:
     out = np.zeros(max(1, n.value), np.uint8)
     check(lib.pbft_wire_encode_votes(*args, out.ctypes.data, n.value, ctypes.byref(n)))
     return out[: n.value]
+
+
+PROPOSE_OK, PROPOSE_GENERAL = 0, 1  # PBFT_PROPOSE_*
+
+
+def pack_requests(ops, timestamps, clients):
+    """Client requests as the arrays the proposal entry points take: (data uint8 -- the operations back to back, padded
+    to a 16-byte multiple --, ops_bytes, op_off uint64[n], op_len uint32[n], timestamp uint64[n], clients uint8[n][64]:
+    each client's bytes, NUL-padded; 64 bytes leave no NUL)."""
+    ops = [bytes(o) for o in ops]
+    n = len(ops)
+    lens = np.array([len(o) for o in ops], np.uint32)
+    offs = np.zeros(n, np.uint64)
+    if n:
+        offs[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
+    raw = b"".join(ops)
+    data = np.frombuffer(raw + bytes((-len(raw)) % 16 or (0 if raw else 16)), np.uint8).copy()
+    cl = np.zeros((n, 64), np.uint8)
+    for i, c in enumerate(clients):
+        c = c.encode() if isinstance(c, str) else bytes(c)
+        assert len(c) <= 64
+        cl[i, :len(c)] = np.frombuffer(c, np.uint8)
+    return data, len(raw), offs, lens, np.ascontiguousarray(timestamps, np.uint64).reshape(n), cl
+
+
+def encode_preprepares(view: int, first_seq: int, requests, replica: int, digests, sigs):
+    """pbft_wire_encode_preprepares: the signed PrePrepares of `requests` (pack_requests' tuple) with sequence numbers
+    first_seq, first_seq + 1, ... as one stream of UviBytes/JSON frames.  Returns (stream uint8, frame_off uint64[n + 1],
+    status uint8[n]: PROPOSE_OK for the canonical form, PROPOSE_GENERAL for any other request)."""
+    lib = load()
+    data, _, offs, lens, ts, cl = requests
+    n = len(lens)
+    d = np.ascontiguousarray(digests, np.uint8).reshape(n, 64)
+    s = np.ascontiguousarray(sigs, np.uint8).reshape(n, 64)
+    need = ctypes.c_size_t()
+    off, st = np.zeros(n + 1, np.uint64), np.zeros(max(n, 1), np.uint8)
+    args = (n, view, first_seq, data.ctypes.data, offs.ctypes.data, lens.ctypes.data, ts.ctypes.data, cl.ctypes.data,
+            replica)
+    check(lib.pbft_wire_encode_preprepares(*args, None, None, None, 0, ctypes.byref(need), None, None))
+    out = np.zeros(max(1, need.value), np.uint8)
+    check(lib.pbft_wire_encode_preprepares(*args, d.ctypes.data, s.ctypes.data, out.ctypes.data, need.value,
+                                           ctypes.byref(need), off.ctypes.data, st.ctypes.data))
+    return out[: need.value], off, st[:n]
