@@ -196,6 +196,10 @@ int pbft_replica_set_log_window(pbft_replica *r, uint64_t log_window);
 /* Encode the 85-byte signed envelope "PBFT" || kind || view LE || seq LE || digest. */
 void pbft_envelope(uint8_t out[PBFT_ENVELOPE_BYTES], uint8_t kind, uint64_t view, uint64_t seq,
                    const uint8_t digest[64]);
+/* The signed message of a client reply: pbft_envelope with kind PBFT_KIND_REPLY = 3 (include/pbft_wire.h) and the
+ * request's timestamp in the sequence number's place; digest = Blake2b-512(C | result) (pbft_reply_digests).  No
+ * vote or PrePrepare path accepts kind 3, so a reply's signature cannot be replayed as either. */
+void pbft_reply_envelope(uint8_t out[PBFT_ENVELOPE_BYTES], uint64_t view, uint64_t timestamp, const uint8_t digest[64]);
 
 /* A PrePrepare for (view, seq) carrying the client operation bytes and the
  * primary's signature (R || S over the kind-0 envelope of the claimed digest),
@@ -409,6 +413,50 @@ typedef struct {
 } pbft_replica_propose_stats;
 int pbft_replica_get_propose_stats(pbft_replica *r, pbft_replica_propose_stats *out);
 
+/* ---- the client's side: committed requests in, signed replies out ----
+ * What inject_node_event does behind committed_local (src/behavior.rs:383-410) for a batch.  The caller has executed the
+ * requests and passes them in execution order; the application owns the execution and the request, the replica keeps
+ * neither (as the reference's State).  Entry i is (seq[i], timestamp[i], the client's 64-byte field clients + 64 * i,
+ * result bytes [res_off[i], res_off[i] + res_len[i]) of results, which must lie inside results_bytes: PBFT_EINVAL).
+ * In order:
+ *   1. (current view, seq[i]) is not committed-local (the predicate of pbft_replica_committed_local: a garbage-collected
+ *      seq this replica committed still counts): status PBFT_REPLY_NOT_COMMITTED, no text;
+ *   2. else timestamp[i] <= last_timestamp: status PBFT_REPLY_STALE, no text -- the reference's discard (:391-398),
+ *      including its single counter per replica (State::last_timestamp, 0 at creation; a per-client table is out of
+ *      scope here as it is there);
+ *   3. else the reply is made (status PBFT_REPLY_OK or PBFT_REPLY_GENERAL, include/pbft_wire.h) and last_timestamp =
+ *      timestamp[i]: a later entry of the same batch is judged against it.
+ * out receives the made replies' texts back to back, byte for byte pbft_wire_encode_replies of them with this replica's
+ * index and PeerId; *len their bytes, reply_off [N + 1] where each lies (an entry without text has length 0), status [N],
+ * *n_replied their number; reply_off, status and n_replied are optional.  The exact length is known before anything is
+ * signed: if cap is smaller, PBFT_EINVAL, *len, reply_off, status and *n_replied are set and nothing changes,
+ * last_timestamp included; out = NULL with cap = 0 is the size query (returns 0, changes nothing).
+ * The texts come from the replier override if one is installed, else from pbft_sign_replies on the replica's signing
+ * clone (pbft_replica_set_signing_seed), else PBFT_EINVAL.  flags: none defined, must be 0.
+ * pbft_replica_set_replier: the override, for replicas and tests without a GPU: fn receives the n replies to make (the
+ * arrays compacted to them), the view and this replica's index, and writes the texts to out (cap bytes) and *len = their
+ * bytes; it returns 0 or a negative code.  fn = NULL removes it.
+ * pbft_replica_set_last_timestamp / pbft_replica_last_timestamp: the counter, for a restart.
+ * What is signed is pbft_reply_envelope (above, next to pbft_envelope). */
+typedef int (*pbft_replier_fn)(void *user, const uint8_t *results, uint64_t results_bytes, const uint64_t *res_off,
+                               const uint32_t *res_len, const uint64_t *timestamp, const char *clients, uint64_t view,
+                               uint64_t n, uint32_t replica, uint8_t *out, size_t cap, size_t *len);
+int pbft_replica_reply(pbft_replica *r, uint64_t N, const uint64_t *seq, const uint64_t *timestamp, const char *clients,
+                       const uint8_t *results, uint64_t results_bytes, const uint64_t *res_off, const uint32_t *res_len,
+                       uint32_t flags, uint8_t *out, size_t cap, size_t *len, uint64_t *reply_off, uint8_t *status,
+                       uint64_t *n_replied);
+int pbft_replica_set_replier(pbft_replica *r, pbft_replier_fn fn, void *user);
+int pbft_replica_set_last_timestamp(pbft_replica *r, uint64_t timestamp);
+int pbft_replica_last_timestamp(pbft_replica *r, uint64_t *out);
+typedef struct {
+  uint64_t replied;       /* replies made by pbft_replica_reply                          */
+  uint64_t calls;         /* pbft_replica_reply calls that went through                  */
+  uint64_t stale;         /* entries discarded by the exactly-once rule in those calls   */
+  uint64_t not_committed; /* entries whose seq was not committed-local in those calls    */
+  uint64_t reply_ns;      /* host time inside those calls                                */
+} pbft_replica_reply_stats;
+int pbft_replica_get_reply_stats(pbft_replica *r, pbft_replica_reply_stats *out);
+
 /* Non-blocking flush.  _submit: collect every READY sub-window (force = every pending candidate) into one
  * batch and launch it; *n_rows = its signatures (0: nothing launched); PBFT_EBUSY while a batch is in flight.
  * _poll: 1 once no batch is in flight -- the finished batch's accepted votes inserted, the events it
@@ -445,6 +493,8 @@ int pbft_replica_get_timings(pbft_replica *r, pbft_replica_timings *out);
 int pbft_key_from_peer_id(const uint8_t *peer_id, size_t len, uint8_t A[32]);
 void pbft_peer_id_from_key(const uint8_t A[32], uint8_t peer_id[PBFT_PEER_ID_BYTES]);
 int pbft_key_from_peer_id_b58(const char *text, size_t len, uint8_t A[32]);
+/* Its inverse: the 52 characters (always 52 for an Ed25519 identity; no NUL is written) of the key's PeerId text. */
+int pbft_peer_id_b58_from_key(const uint8_t A[32], char out[52]);
 int pbft_replica_peer_index(pbft_replica *r, const uint8_t *peer_id, size_t len);
 
 #ifdef __cplusplus

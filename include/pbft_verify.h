@@ -378,6 +378,8 @@ int pbft_sign_batch(pbft_ctx *ctx, const uint8_t *seeds, uint32_t n_seeds, const
  * seed is expanded once, by a one-lane kernel -- SHA-512(seed) -> the clamped scalar a and the prefix, A = [a]B --
  * and the 96 bytes a || prefix || A stay in a device buffer of the context with the replica index (<= 65535) that the
  * frames carry; the seed's device staging is zeroed by that kernel.  pub_out (optional, 32 bytes) receives A.
+ * The 52 characters of A's PeerId text (pbft_peer_id_b58_from_key), computed on the host from the key that came
+ * back, are stored next to it for the client replies (pbft_sign_replies*).
  * seed = NULL clears the state (the buffer is zeroed).  Blocking; PBFT_EBUSY while an async batch is in flight.
  * A clone (pbft_verify_ctx_clone) does not inherit the seed.  The signing kernels index their tables by secret
  * digits, as pbft_sign_batch's do: not constant-time against a co-tenant of the GPU. */

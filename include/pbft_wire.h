@@ -501,6 +501,101 @@ int pbft_sign_preprepares_frames(pbft_ctx *ctx, const uint8_t *ops, uint64_t ops
                                  uint64_t first_seq, uint64_t N, uint8_t *out, size_t cap, size_t *len,
                                  uint64_t *frame_off, uint8_t *digests, uint8_t *sigs, uint8_t *status);
 
+/* ---- client replies: committed requests in, signed replies out (kernels: pbft_amd/csrc/reply.hip; text rule:
+ * reply_core.h) ----
+ * What inject_node_event does behind committed_local (src/behavior.rs:382-411) once the request is executed: the
+ * ClientReply (src/message.rs:54-103), here signed.  Reply i = result bytes [res_off[i], res_off[i] + res_len[i]) of
+ * `results`, timestamp[i] and the client's 64-byte field clients + 64 * i (as pbft_wire_encode_preprepares takes it).
+ * Its text is the reference's serialization in the reference's field order, then the two fields of every signed message:
+ *   {"view":V,"timestamp":T,"peer_id":"<52 base58 chars>","result":"R","replica":I,"signature":"<128 hex>"}
+ * with no varint in front: the reference writes reply.to_string() raw, one reply per connection
+ * (src/client_handler.rs:75-84).  The signature is RFC 8032 over pbft_reply_envelope(view, timestamp, D),
+ *   "PBFT" | 3 | view LE | timestamp LE | D,   D = Blake2b-512(C[64] | result bytes),
+ * where C is the client field with everything from its first NUL on replaced by zeros (a field without a NUL is taken
+ * whole).  The serialized reply does not carry the client; D binds it, so f + 1 replies to one client cannot be replayed
+ * to another whose request has the same timestamp.  Kind 3 cannot be replayed as a vote or a PrePrepare: the egress rule
+ * (eg_env_kind) answers 0 for it and the admission path knows kinds 0 .. 2 only.
+ * A reply is canonical when its result has 0 .. PBFT_REPLY_RESULT_MAX bytes, all of them 0x20 .. 0x7E other than '"'
+ * and '\': its text needs no escaping. */
+#define PBFT_KIND_REPLY 3
+#define PBFT_REPLY_RESULT_MAX 3072
+#define PBFT_REPLY_PEER_ID_CHARS 52
+#define PBFT_REPLY_OK 0            /* canonical: the core's text                                                    */
+#define PBFT_REPLY_GENERAL 1       /* any other result: the serde-exact string escaper; the device forms write none */
+#define PBFT_REPLY_STALE 2         /* pbft_replica_reply only: timestamp <= last_timestamp, no text                 */
+#define PBFT_REPLY_NOT_COMMITTED 3 /* pbft_replica_reply only: (view, seq) is not committed-local, no text          */
+
+/* Host, no context and no GPU: digests_out[i] = D of reply i as defined above.  PBFT_EINVAL: a null argument, a result
+ * outside results_bytes. */
+int pbft_reply_digests(uint64_t N, const char *clients /* [N][64] */, const uint8_t *results, uint64_t results_bytes,
+                       const uint64_t *res_off, const uint32_t *res_len, uint8_t *digests_out /* [N][64] */);
+
+/* Host, no context and no GPU: the N signed replies' texts back to back, the reference form of the functions below.  A
+ * canonical result takes the core's writer (PBFT_REPLY_OK); any other goes through the codec's serde-exact string
+ * escaper (PBFT_REPLY_GENERAL).  A result that is not valid UTF-8 is treated as pbft_wire_encode_preprepares treats such
+ * an operation: its bytes >= 0x80 are written as they are and nothing is validated (serde could not have produced such a
+ * String; a JSON parser will refuse the text).  *len = the full length; returns 0, or PBFT_EINVAL if cap is too small
+ * (then *len, reply_off and status are still set), replica > 65535 or an argument is null.  sigs may be NULL for the
+ * length query (out = NULL, cap = 0): no text's length depends on it; peer_id may then be NULL too.  reply_off [N + 1]
+ * (reply i occupies [reply_off[i], reply_off[i + 1])) and status [N] are optional and complete whatever cap is. */
+int pbft_wire_encode_replies(uint64_t N, uint64_t view, const uint64_t *timestamp, const uint8_t *results,
+                             const uint64_t *res_off, const uint32_t *res_len, uint32_t replica,
+                             const char *peer_id /* [52] */, const uint8_t *sigs /* [N][64] */, uint8_t *out, size_t cap,
+                             size_t *len, uint64_t *reply_off, uint8_t *status);
+
+/* The reader-side twin, for clients and tests: a byte-for-byte matcher of the canonical text, one reply, no context.
+ * PBFT_RH_OK implies that the writer, given the same fields, writes the same bytes.  Anything else -- whitespace, another
+ * field order, an escape, a 51-character peer id, an uppercase hex digit, a trailing byte, a result above
+ * PBFT_REPLY_RESULT_MAX -- is PBFT_RH_NONE (a general JSON parser decides).  peer_id is the text as it stands
+ * (pbft_key_from_peer_id_b58 gives the key).  Returns 0 (the answer is out->status) or PBFT_EINVAL for a null argument. */
+#define PBFT_RH_NONE 0
+#define PBFT_RH_OK 1
+typedef struct {
+  uint64_t view, timestamp;
+  uint32_t result_off, result_len; /* the result's bytes, counted from the text's first byte */
+  uint32_t replica;
+  uint32_t status; /* PBFT_RH_* */
+  char peer_id[PBFT_REPLY_PEER_ID_CHARS];
+  uint8_t sig[64];
+  uint8_t pad[4];
+} pbft_reply_head; /* all zero when status is PBFT_RH_NONE */
+int pbft_wire_decode_reply(const uint8_t *text, size_t len, pbft_reply_head *out);
+
+/* Device form, enqueue only on `stream` (NULL = the context's): three kernel nodes -- the canonical test, the text
+ * lengths and their scan inside each 64-reply tile; the scan over the tiles; one digest and one signature per lane and
+ * the texts -- with no allocation, copy, memset or synchronisation once pbft_reply_reserve(max_n >= N) has sized the
+ * workspace (8 bytes per 64 replies); every loop is bounded; no lane waits for another block; capturable as a plain
+ * chain.  The signer and the "peer_id" are the identity of pbft_sign_set_seed (PBFT_EINVAL without one), "replica" the
+ * index given there.  N <= 2^24.
+ * Per reply i, whatever its form: d_digests[i] = D, d_sigs[i] = the signature over the kind-3 envelope.  A result that
+ * does not lie inside results_bytes is not read: digest and signature zero, status PBFT_REPLY_GENERAL.
+ * A canonical reply has status PBFT_REPLY_OK and its text at d_out + d_reply_off[i]; any other has status
+ * PBFT_REPLY_GENERAL and length 0; d_reply_off[N] is the total.  The texts equal pbft_wire_encode_replies restricted to
+ * the OK replies.  When the stream would exceed out_cap, the replies that do not fit entirely are not written, none is
+ * written in part, nothing at or beyond d_out + out_cap is touched, and d_reply_off, d_digests, d_sigs and d_status are
+ * still complete.
+ * d_out may have any alignment; d_results is 16-byte aligned and nothing outside [d_results, round_up(results_bytes, 4))
+ * is read; d_res_off, d_timestamp, d_reply_off 8-byte aligned, d_res_len, d_digests, d_sigs 4-byte.  PBFT_EINVAL: a null
+ * or misaligned pointer, N > 2^24; a refused call has enqueued nothing.  Calls of one context share the workspace and
+ * must be ordered, like its other launches. */
+int pbft_reply_reserve(pbft_ctx *ctx, uint64_t max_n);
+int pbft_sign_replies_device(pbft_ctx *ctx, const uint8_t *d_results, uint64_t results_bytes, const uint64_t *d_res_off,
+                             const uint32_t *d_res_len, const uint64_t *d_timestamp, const uint8_t *d_clients,
+                             uint64_t view, uint64_t N, uint8_t *d_out, uint64_t out_cap, uint64_t *d_reply_off,
+                             uint8_t *d_digests, uint8_t *d_sigs, uint8_t *d_status, void *stream);
+/* Blocking, host buffers; the complete form: its output equals pbft_wire_encode_replies for every input, with the
+ * digests and signatures made on the device.  *len = the bytes needed and the status, computed on the host before
+ * anything runs; when cap is smaller: PBFT_EINVAL, nothing written and nothing launched; out = NULL with cap = 0 is
+ * the size query and returns 0, as pbft_wire_encode_replies and pbft_replica_reply do.  If any status is
+ * PBFT_REPLY_GENERAL the stream is completed on the host: the device's replies in order, the others written by the
+ * host encoder from the signature that came back.  reply_off [N + 1], digests, sigs [N][64] and status [N] are
+ * optional.  PBFT_EINVAL also for a result outside results_bytes; PBFT_EBUSY while an async batch is in flight on the
+ * context. */
+int pbft_sign_replies(pbft_ctx *ctx, const uint8_t *results, uint64_t results_bytes, const uint64_t *res_off,
+                      const uint32_t *res_len, const uint64_t *timestamp, const char *clients, uint64_t view, uint64_t N,
+                      uint8_t *out, size_t cap, size_t *len, uint64_t *reply_off, uint8_t *digests, uint8_t *sigs,
+                      uint8_t *status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -129,6 +129,44 @@ pub type pbft_proposer_fn = Option<unsafe extern "C" fn(user: *mut c_void, ops: 
                                                          first_seq: u64, n: u64, replica: u32, out: *mut u8,
                                                          cap: usize, len: *mut usize, digests: *mut u8,
                                                          sigs: *mut u8) -> c_int>;
+/// Counters of the client's side (pbft_replica_get_reply_stats).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct pbft_replica_reply_stats {
+    pub replied: u64,
+    pub calls: u64,
+    pub stale: u64,
+    pub not_committed: u64,
+    pub reply_ns: u64,
+}
+pub const PBFT_KIND_REPLY: u8 = 3;
+pub const PBFT_REPLY_OK: u8 = 0;
+pub const PBFT_REPLY_GENERAL: u8 = 1;
+pub const PBFT_REPLY_STALE: u8 = 2;
+pub const PBFT_REPLY_NOT_COMMITTED: u8 = 3;
+pub const PBFT_RH_NONE: u32 = 0;
+pub const PBFT_RH_OK: u32 = 1;
+/// What pbft_wire_decode_reply answers (include/pbft_wire.h pbft_reply_head).
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct pbft_reply_head {
+    pub view: u64,
+    pub timestamp: u64,
+    pub result_off: u32,
+    pub result_len: u32,
+    pub replica: u32,
+    pub status: u32,
+    pub peer_id: [u8; 52],
+    pub sig: [u8; 64],
+    pub pad: [u8; 4],
+}
+/// Replier override of pbft_replica_set_replier: (user, results, results_bytes, res_off, res_len, timestamp, clients,
+/// view, n, replica, out, cap, len).
+pub type pbft_replier_fn = Option<unsafe extern "C" fn(user: *mut c_void, results: *const u8, results_bytes: u64,
+                                                        res_off: *const u64, res_len: *const u32,
+                                                        timestamp: *const u64, clients: *const c_char, view: u64,
+                                                        n: u64, replica: u32, out: *mut u8, cap: usize,
+                                                        len: *mut usize) -> c_int>;
 pub const PBFT_ADMIT_CLEAN: u8 = 0;
 pub const PBFT_ADMIT_CONTESTED: u8 = 1;
 pub const PBFT_ADMIT_REJ_VIEW: u8 = 2;
@@ -562,4 +600,31 @@ extern "C" {
     pub fn pbft_replica_set_next_seq(r: *mut pbft_replica, seq: u64) -> c_int;
     pub fn pbft_replica_set_proposer(r: *mut pbft_replica, f: pbft_proposer_fn, user: *mut c_void) -> c_int;
     pub fn pbft_replica_get_propose_stats(r: *mut pbft_replica, out: *mut pbft_replica_propose_stats) -> c_int;
+    pub fn pbft_reply_envelope(out: *mut u8, view: u64, timestamp: u64, digest: *const u8);
+    pub fn pbft_peer_id_b58_from_key(a: *const u8, out: *mut c_char) -> c_int;
+    pub fn pbft_reply_digests(n: u64, clients: *const c_char, results: *const u8, results_bytes: u64,
+                              res_off: *const u64, res_len: *const u32, digests_out: *mut u8) -> c_int;
+    pub fn pbft_wire_encode_replies(n: u64, view: u64, timestamp: *const u64, results: *const u8, res_off: *const u64,
+                                    res_len: *const u32, replica: u32, peer_id: *const c_char, sigs: *const u8,
+                                    out: *mut u8, cap: usize, len: *mut usize, reply_off: *mut u64,
+                                    status: *mut u8) -> c_int;
+    pub fn pbft_wire_decode_reply(text: *const u8, len: usize, out: *mut pbft_reply_head) -> c_int;
+    pub fn pbft_reply_reserve(ctx: *mut pbft_ctx, max_n: u64) -> c_int;
+    pub fn pbft_sign_replies_device(ctx: *mut pbft_ctx, d_results: *const u8, results_bytes: u64,
+                                    d_res_off: *const u64, d_res_len: *const u32, d_timestamp: *const u64,
+                                    d_clients: *const u8, view: u64, n: u64, d_out: *mut u8, out_cap: u64,
+                                    d_reply_off: *mut u64, d_digests: *mut u8, d_sigs: *mut u8, d_status: *mut u8,
+                                    stream: *mut c_void) -> c_int;
+    pub fn pbft_sign_replies(ctx: *mut pbft_ctx, results: *const u8, results_bytes: u64, res_off: *const u64,
+                             res_len: *const u32, timestamp: *const u64, clients: *const c_char, view: u64, n: u64,
+                             out: *mut u8, cap: usize, len: *mut usize, reply_off: *mut u64, digests: *mut u8,
+                             sigs: *mut u8, status: *mut u8) -> c_int;
+    pub fn pbft_replica_reply(r: *mut pbft_replica, n: u64, seq: *const u64, timestamp: *const u64,
+                              clients: *const c_char, results: *const u8, results_bytes: u64, res_off: *const u64,
+                              res_len: *const u32, flags: u32, out: *mut u8, cap: usize, len: *mut usize,
+                              reply_off: *mut u64, status: *mut u8, n_replied: *mut u64) -> c_int;
+    pub fn pbft_replica_set_replier(r: *mut pbft_replica, f: pbft_replier_fn, user: *mut c_void) -> c_int;
+    pub fn pbft_replica_set_last_timestamp(r: *mut pbft_replica, timestamp: u64) -> c_int;
+    pub fn pbft_replica_last_timestamp(r: *mut pbft_replica, out: *mut u64) -> c_int;
+    pub fn pbft_replica_get_reply_stats(r: *mut pbft_replica, out: *mut pbft_replica_reply_stats) -> c_int;
 }

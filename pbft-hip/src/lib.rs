@@ -1005,6 +1005,47 @@ impl<'a> Replica<'a> {
         unsafe { ffi::pbft_replica_get_propose_stats(self.raw, &mut s) };
         s
     }
+    /// The client's side of a round (pbft_replica_reply): after the events loop the caller executes the requests whose
+    /// (view, seq) reported COMMITTED_LOCAL and passes them in execution order: `seqs[i]` with the request's timestamp
+    /// and client in `executed[i]` and the result in its `operation` field.  Entries that are not committed-local or
+    /// whose timestamp is not above the last reply's are skipped (exactly-once, src/behavior.rs:391-398).  Returns the
+    /// signed replies' texts back to back, where each lies (reply i at [reply_off[i], reply_off[i + 1]), empty when
+    /// skipped) and the per-entry status (ffi::PBFT_REPLY_*); each text goes to its client's connection.
+    pub fn reply(&mut self, seqs: &[u64], executed: &[ClientRequest]) -> Result<(Vec<u8>, Vec<u64>, Vec<u8>)> {
+        assert_eq!(seqs.len(), executed.len());
+        let p = PackedRequests::new(executed);
+        let n = seqs.len();
+        let (mut len, mut made) = (0usize, 0u64);
+        check(unsafe {
+            ffi::pbft_replica_reply(self.raw, n as u64, seqs.as_ptr(), p.ts.as_ptr(), p.clients.as_ptr() as *const c_char,
+                                    p.ops.as_ptr(), p.ops_bytes, p.off.as_ptr(), p.len.as_ptr(), 0, ptr::null_mut(), 0,
+                                    &mut len, ptr::null_mut(), ptr::null_mut(), &mut made)
+        })?;
+        let mut out = vec![0u8; len.max(1)];
+        let mut off = vec![0u64; n + 1];
+        let mut status = vec![0u8; n];
+        check(unsafe {
+            ffi::pbft_replica_reply(self.raw, n as u64, seqs.as_ptr(), p.ts.as_ptr(), p.clients.as_ptr() as *const c_char,
+                                    p.ops.as_ptr(), p.ops_bytes, p.off.as_ptr(), p.len.as_ptr(), 0, out.as_mut_ptr(),
+                                    len, &mut len, off.as_mut_ptr(), status.as_mut_ptr(), &mut made)
+        })?;
+        out.truncate(len);
+        Ok((out, off, status))
+    }
+    /// The timestamp of the last reply (State::last_timestamp; 0 at creation), to save and restore over a restart.
+    pub fn last_timestamp(&self) -> u64 {
+        let mut t = 0u64;
+        unsafe { ffi::pbft_replica_last_timestamp(self.raw, &mut t) };
+        t
+    }
+    pub fn set_last_timestamp(&mut self, timestamp: u64) -> Result<()> {
+        check(unsafe { ffi::pbft_replica_set_last_timestamp(self.raw, timestamp) }).map(|_| ())
+    }
+    pub fn reply_stats(&self) -> ffi::pbft_replica_reply_stats {
+        let mut s = ffi::pbft_replica_reply_stats::default();
+        unsafe { ffi::pbft_replica_get_reply_stats(self.raw, &mut s) };
+        s
+    }
     pub fn egress_stats(&self) -> ffi::pbft_replica_egress_stats {
         let mut s = ffi::pbft_replica_egress_stats::default();
         unsafe { ffi::pbft_replica_get_egress_stats(self.raw, &mut s) };

@@ -37,6 +37,9 @@ EXPORTS = (
     # include/pbft_wire.h, the primary's proposals
     "pbft_wire_encode_preprepares", "pbft_propose_reserve", "pbft_sign_preprepares_frames_device",
     "pbft_sign_preprepares_frames",
+    # include/pbft_wire.h, the client replies
+    "pbft_reply_digests", "pbft_wire_encode_replies", "pbft_wire_decode_reply", "pbft_reply_reserve",
+    "pbft_sign_replies_device", "pbft_sign_replies",
 )
 
 ERRORS = {0: "PBFT_OK", -1: "PBFT_EINVAL", -2: "PBFT_EHIP", -3: "PBFT_ENOKEYS",
@@ -162,6 +165,12 @@ def load() -> ctypes.CDLL:
                                                       vp, vp]),
         "pbft_sign_preprepares_frames": (i32, [vp, vp, u64, vp, vp, vp, vp, u64, u64, u64, vp, ctypes.c_size_t, vp, vp,
                                                vp, vp, vp]),
+        "pbft_reply_digests": (i32, [u64, vp, vp, u64, vp, vp, vp]),
+        "pbft_wire_encode_replies": (i32, [u64, u64, vp, vp, vp, vp, u32, vp, vp, vp, ctypes.c_size_t, vp, vp, vp]),
+        "pbft_wire_decode_reply": (i32, [vp, ctypes.c_size_t, vp]),
+        "pbft_reply_reserve": (i32, [vp, u64]),
+        "pbft_sign_replies_device": (i32, [vp, vp, u64, vp, vp, vp, vp, u64, u64, vp, u64, vp, vp, vp, vp, vp]),
+        "pbft_sign_replies": (i32, [vp, vp, u64, vp, vp, vp, vp, u64, u64, vp, ctypes.c_size_t, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

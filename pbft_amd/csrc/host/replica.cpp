@@ -47,6 +47,7 @@
 #include "../admit_core.h"
 #include "../wire_decode_core.h"
 #include "../egress_core.h"
+#include "../reply_core.h"
 
 // The device half of pbft_replica_push_streams lives in the GPU library (pbft_verify.hip).  Weak, so that this file
 // still links on its own into the host-only programs that test the state machine: there the symbols are null and a
@@ -65,6 +66,8 @@
 // ... and of the primary's PrePrepares (propose.hip): without it only a proposer override (pbft_replica_set_proposer)
 // proposes.
 #pragma weak pbft_sign_preprepares_frames
+// ... and of the client replies (reply.hip): without it only a replier override (pbft_replica_set_replier) replies.
+#pragma weak pbft_sign_replies
 
 namespace {
 
@@ -560,6 +563,11 @@ struct pbft_replica {
   void* proposer_user = nullptr;
   std::vector<uint8_t> prop_digests, prop_sigs;  // of the call (loopback)
   pbft_replica_propose_stats pstats{};
+  // the client's side (pbft_replica_reply): State::last_timestamp (src/state.rs:12-13, 0 at creation)
+  uint64_t last_timestamp = 0;
+  pbft_replier_fn replier_fn = nullptr;
+  void* replier_user = nullptr;
+  pbft_replica_reply_stats rstats{};
 };
 
 static uint32_t primary_of(const pbft_replica* r, uint64_t view) { return (uint32_t)(view % r->n); }
@@ -3308,6 +3316,122 @@ int pbft_replica_get_propose_stats(pbft_replica* r, pbft_replica_propose_stats* 
   return PBFT_OK;
 }
 
+// ---- the client's side: committed requests in, signed replies out (include/pbft_replica.h) ----
+void pbft_reply_envelope(uint8_t out[PBFT_ENVELOPE_BYTES], uint64_t view, uint64_t timestamp, const uint8_t digest[64]) {
+  pbft_envelope(out, PBFT_KIND_REPLY, view, timestamp, digest);
+}
+
+int pbft_replica_set_replier(pbft_replica* r, pbft_replier_fn fn, void* user) {
+  if (!r) return PBFT_EINVAL;
+  r->replier_fn = fn;
+  r->replier_user = fn ? user : nullptr;
+  return PBFT_OK;
+}
+
+int pbft_replica_set_last_timestamp(pbft_replica* r, uint64_t timestamp) {
+  if (!r) return PBFT_EINVAL;
+  r->last_timestamp = timestamp;
+  return PBFT_OK;
+}
+
+int pbft_replica_last_timestamp(pbft_replica* r, uint64_t* out) {
+  if (!r || !out) return PBFT_EINVAL;
+  *out = r->last_timestamp;
+  return PBFT_OK;
+}
+
+int pbft_replica_reply(pbft_replica* r, uint64_t N, const uint64_t* seq, const uint64_t* timestamp, const char* clients,
+                       const uint8_t* results, uint64_t results_bytes, const uint64_t* res_off, const uint32_t* res_len,
+                       uint32_t flags, uint8_t* out, size_t cap, size_t* len, uint64_t* reply_off, uint8_t* status,
+                       uint64_t* n_replied) {
+  if (!r || flags || (cap && !out) || (results_bytes && !results) ||
+      (N && (!seq || !timestamp || !clients || !res_off || !res_len)))
+    return PBFT_EINVAL;
+  if (len) *len = 0;
+  if (n_replied) *n_replied = 0;
+  for (uint64_t i = 0; i < N; ++i)
+    if (res_len[i] > results_bytes || res_off[i] > results_bytes - res_len[i]) return PBFT_EINVAL;
+  const auto t0 = std::chrono::steady_clock::now();
+  const uint64_t view = r->current_view;
+  // which replies are made: committed-local (the predicate of pbft_replica_committed_local), then the exactly-once rule
+  // against the single counter, which moves inside the batch (src/behavior.rs:383-398, :409)
+  std::vector<uint8_t> st(N ? N : 1);
+  std::vector<uint64_t> m_ts, m_off;
+  std::vector<uint32_t> m_len;
+  std::vector<char> m_cl;
+  uint64_t last = r->last_timestamp, n_stale = 0, n_uncommitted = 0;
+  for (uint64_t i = 0; i < N; ++i) {
+    const Window* w = find_window(r, view, seq[i]);
+    const bool committed = w ? is_committed_local(r, view, *w) : is_done(r, view, seq[i]);
+    if (!committed) {
+      st[i] = PBFT_REPLY_NOT_COMMITTED;
+      ++n_uncommitted;
+    } else if (timestamp[i] <= last) {
+      st[i] = PBFT_REPLY_STALE;
+      ++n_stale;
+    } else {
+      st[i] = PBFT_REPLY_OK;  // (OK or GENERAL: the encoder says which)
+      last = timestamp[i];
+      m_ts.push_back(timestamp[i]);
+      m_off.push_back(res_off[i]);
+      m_len.push_back(res_len[i]);
+      m_cl.insert(m_cl.end(), clients + 64 * i, clients + 64 * i + 64);
+    }
+  }
+  const uint64_t n = m_ts.size();
+  // the exact length, before anything is signed
+  std::vector<uint64_t> m_roff(n + 1);
+  std::vector<uint8_t> m_st(n ? n : 1);
+  size_t need = 0;
+  if (pbft_wire_encode_replies(n, view, m_ts.data(), results, m_off.data(), m_len.data(), r->self, nullptr, nullptr,
+                               nullptr, 0, &need, m_roff.data(), m_st.data()) != 0)
+    return PBFT_EINVAL;
+  for (uint64_t i = 0, k = 0; i < N; ++i) {
+    const bool made = st[i] == PBFT_REPLY_OK;
+    if (reply_off) reply_off[i] = k < n ? m_roff[k] : need;
+    if (made) st[i] = m_st[k++];
+    if (status) status[i] = st[i];
+  }
+  if (reply_off) reply_off[N] = need;
+  if (len) *len = need;
+  if (n_replied) *n_replied = n;
+  if (!out && cap == 0) return PBFT_OK;  // the size query
+  if (cap < need) return PBFT_EINVAL;   // nothing changes, last_timestamp included
+  if (n) {
+    size_t got = 0;
+    int rc;
+    if (r->replier_fn) {
+      rc = r->replier_fn(r->replier_user, results, results_bytes, m_off.data(), m_len.data(), m_ts.data(), m_cl.data(),
+                         view, n, r->self, out, cap, &got);
+    } else {
+      if (!r->seed_set || !r->dctx) rc = PBFT_EINVAL;  // no signer (pbft_replica_set_signing_seed)
+      else if (!pbft_sign_replies) rc = PBFT_ENODEV;
+      else
+        rc = pbft_sign_replies(r->dctx, results, results_bytes, m_off.data(), m_len.data(), m_ts.data(), m_cl.data(),
+                               view, n, out, cap, &got, nullptr, nullptr, nullptr, nullptr);
+    }
+    if (rc == PBFT_OK && got != need) rc = PBFT_EINVAL;  // (not the texts of these replies)
+    if (rc != PBFT_OK) {
+      if (len) *len = 0;
+      if (n_replied) *n_replied = 0;
+      return rc;
+    }
+  }
+  r->last_timestamp = last;
+  r->rstats.replied += n;
+  r->rstats.stale += n_stale;
+  r->rstats.not_committed += n_uncommitted;
+  ++r->rstats.calls;
+  r->rstats.reply_ns += ns_since(t0);
+  return PBFT_OK;
+}
+
+int pbft_replica_get_reply_stats(pbft_replica* r, pbft_replica_reply_stats* out) {
+  if (!r || !out) return PBFT_EINVAL;
+  *out = r->rstats;
+  return PBFT_OK;
+}
+
 int pbft_replica_get_pp_stats(pbft_replica* r, pbft_replica_pp_stats* out) {
   if (!r || !out) return PBFT_EINVAL;
   *out = r->ppstats;
@@ -3393,6 +3517,11 @@ int pbft_key_from_peer_id_b58(const char* text, size_t len, uint8_t A[32]) {
   uint8_t raw[PBFT_PEER_ID_BYTES] = {0};
   memcpy(raw + zeros, num + lead, body);
   return pbft_key_from_peer_id(raw, PBFT_PEER_ID_BYTES, A);
+}
+
+int pbft_peer_id_b58_from_key(const uint8_t A[32], char out[PBFT_REPLY_PEER_ID_CHARS]) {
+  if (!A || !out) return PBFT_EINVAL;
+  return pbft::rp_peer_id_b58(A, (uint8_t*)out) == pbft::RP_PEER_ID_B58 ? PBFT_OK : PBFT_EINVAL;
 }
 
 int pbft_replica_peer_index(pbft_replica* r, const uint8_t* peer_id, size_t len) {

@@ -20,6 +20,7 @@
 
 #include "../../../include/pbft_replica.h"
 #include "../propose_core.h"
+#include "../reply_core.h"
 
 namespace {
 
@@ -778,6 +779,176 @@ int pbft_wire_encode_preprepares(uint64_t N, uint64_t view, uint64_t first_seq, 
   if (frame_off) frame_off[N] = off;
   *len = off;
   return query ? 0 : rc;
+}
+
+// ---- client replies (include/pbft_wire.h; text rule: reply_core.h) ----
+namespace {
+
+// Blake2b-512 (RFC 7693, unkeyed) of two byte strings back to back, for the reply digest D = H(C | result); the
+// device's form is digest_kernels.h's.
+struct Blake2b {
+  uint64_t h[8];
+  uint8_t buf[128];
+  size_t fill = 0;
+  uint64_t t = 0;
+  static uint64_t rotr(uint64_t x, int n) { return (x >> n) | (x << (64 - n)); }
+  Blake2b() {
+    static const uint64_t IV[8] = {0x6a09e667f3bcc908ULL, 0xbb67ae8584caa73bULL, 0x3c6ef372fe94f82bULL,
+                                   0xa54ff53a5f1d36f1ULL, 0x510e527fade682d1ULL, 0x9b05688c2b3e6c1fULL,
+                                   0x1f83d9abfb41bd6bULL, 0x5be0cd19137e2179ULL};
+    memcpy(h, IV, sizeof h);
+    h[0] ^= 0x01010040ULL;
+  }
+  void compress(bool last) {
+    static const uint64_t IV[8] = {0x6a09e667f3bcc908ULL, 0xbb67ae8584caa73bULL, 0x3c6ef372fe94f82bULL,
+                                   0xa54ff53a5f1d36f1ULL, 0x510e527fade682d1ULL, 0x9b05688c2b3e6c1fULL,
+                                   0x1f83d9abfb41bd6bULL, 0x5be0cd19137e2179ULL};
+    static const uint8_t SIG[12][16] = {
+        {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15}, {14, 10, 4, 8, 9, 15, 13, 6, 1, 12, 0, 2, 11, 7, 5, 3},
+        {11, 8, 12, 0, 5, 2, 15, 13, 10, 14, 3, 6, 7, 1, 9, 4}, {7, 9, 3, 1, 13, 12, 11, 14, 2, 6, 5, 10, 4, 0, 15, 8},
+        {9, 0, 5, 7, 2, 4, 10, 15, 14, 1, 11, 12, 6, 8, 3, 13}, {2, 12, 6, 10, 0, 11, 8, 3, 4, 13, 7, 5, 15, 14, 1, 9},
+        {12, 5, 1, 15, 14, 13, 4, 10, 0, 7, 6, 3, 9, 2, 8, 11}, {13, 11, 7, 14, 12, 1, 3, 9, 5, 0, 15, 4, 8, 6, 2, 10},
+        {6, 15, 14, 9, 11, 3, 0, 8, 12, 2, 13, 7, 1, 4, 10, 5}, {10, 2, 8, 4, 7, 6, 1, 5, 15, 11, 9, 14, 3, 12, 13, 0},
+        {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15}, {14, 10, 4, 8, 9, 15, 13, 6, 1, 12, 0, 2, 11, 7, 5, 3}};
+    uint64_t m[16], v[16];
+    for (int i = 0; i < 16; ++i) {
+      m[i] = 0;
+      for (int j = 7; j >= 0; --j) m[i] = (m[i] << 8) | buf[8 * i + j];
+    }
+    for (int i = 0; i < 8; ++i) { v[i] = h[i]; v[8 + i] = IV[i]; }
+    v[12] ^= t;
+    if (last) v[14] = ~v[14];
+    auto G = [&](int a, int b, int c, int d, uint64_t x, uint64_t y) {
+      v[a] = v[a] + v[b] + x; v[d] = rotr(v[d] ^ v[a], 32);
+      v[c] = v[c] + v[d];     v[b] = rotr(v[b] ^ v[c], 24);
+      v[a] = v[a] + v[b] + y; v[d] = rotr(v[d] ^ v[a], 16);
+      v[c] = v[c] + v[d];     v[b] = rotr(v[b] ^ v[c], 63);
+    };
+    for (int r = 0; r < 12; ++r) {
+      const uint8_t* s = SIG[r];
+      G(0, 4, 8, 12, m[s[0]], m[s[1]]);   G(1, 5, 9, 13, m[s[2]], m[s[3]]);
+      G(2, 6, 10, 14, m[s[4]], m[s[5]]);  G(3, 7, 11, 15, m[s[6]], m[s[7]]);
+      G(0, 5, 10, 15, m[s[8]], m[s[9]]);  G(1, 6, 11, 12, m[s[10]], m[s[11]]);
+      G(2, 7, 8, 13, m[s[12]], m[s[13]]); G(3, 4, 9, 14, m[s[14]], m[s[15]]);
+    }
+    for (int i = 0; i < 8; ++i) h[i] ^= v[i] ^ v[8 + i];
+  }
+  void update(const uint8_t* p, size_t n) {
+    while (n) {
+      if (fill == 128) {  // (a full buffer is compressed only when more follows: the last block is final's)
+        t += 128;
+        compress(false);
+        fill = 0;
+      }
+      const size_t k = n < 128 - fill ? n : 128 - fill;
+      memcpy(buf + fill, p, k);
+      fill += k;
+      p += k;
+      n -= k;
+    }
+  }
+  void final(uint8_t out[64]) {
+    t += fill;
+    memset(buf + fill, 0, 128 - fill);
+    compress(true);
+    for (int i = 0; i < 8; ++i)
+      for (int j = 0; j < 8; ++j) out[8 * i + j] = (uint8_t)(h[i] >> (8 * j));
+  }
+};
+
+}  // namespace
+
+int pbft_reply_digests(uint64_t N, const char* clients, const uint8_t* results, uint64_t results_bytes,
+                       const uint64_t* res_off, const uint32_t* res_len, uint8_t* digests_out) {
+  if (N && (!clients || !res_off || !res_len || !digests_out)) return PBFT_EINVAL;
+  if (results_bytes && !results) return PBFT_EINVAL;
+  for (uint64_t i = 0; i < N; ++i)
+    if (res_len[i] > results_bytes || res_off[i] > results_bytes - res_len[i]) return PBFT_EINVAL;
+  for (uint64_t i = 0; i < N; ++i) {
+    uint8_t c[pbft::RP_CLIENT_FIELD];
+    pbft::rp_client_norm(c, (const uint8_t*)clients + pbft::RP_CLIENT_FIELD * i);
+    Blake2b b;
+    b.update(c, sizeof c);
+    if (res_len[i]) b.update(results + res_off[i], res_len[i]);
+    b.final(digests_out + 64 * i);
+  }
+  return 0;
+}
+
+int pbft_wire_encode_replies(uint64_t N, uint64_t view, const uint64_t* timestamp, const uint8_t* results,
+                             const uint64_t* res_off, const uint32_t* res_len, uint32_t replica, const char* peer_id,
+                             const uint8_t* sigs, uint8_t* out, size_t cap, size_t* len, uint64_t* reply_off,
+                             uint8_t* status) {
+  if (!len) return PBFT_EINVAL;
+  *len = 0;
+  if ((!out && cap) || replica > pbft::RP_MAX_REPLICA) return PBFT_EINVAL;
+  if (N && (!timestamp || !res_off || !res_len)) return PBFT_EINVAL;
+  const bool query = !out && cap == 0;
+  if (N && !query && (!sigs || !peer_id)) return PBFT_EINVAL;
+  static const uint8_t zero[64] = {0};
+  static const char no_peer[pbft::RP_PEER_ID_B58 + 1] = "1111111111111111111111111111111111111111111111111111";
+  const uint8_t* pid = (const uint8_t*)(peer_id ? peer_id : no_peer);
+  size_t off = 0;
+  int rc = 0;
+  for (uint64_t i = 0; i < N; ++i) {
+    const uint8_t* res = results ? results + res_off[i] : nullptr;
+    if (!res && res_len[i]) return PBFT_EINVAL;
+    const uint8_t* sg = sigs ? sigs + 64 * i : zero;
+    if (reply_off) reply_off[i] = off;
+    size_t tl = 0;
+    if (pbft::rp_canonical(res, res_len[i])) {
+      if (status) status[i] = PBFT_REPLY_OK;
+      tl = pbft::rp_text_len(view, timestamp[i], replica, res_len[i]);
+      if (out && off <= cap && cap - off >= tl) {
+        uint32_t sw[16];
+        memcpy(sw, sg, 64);
+        uint8_t* dst = out + off;
+        auto put = [dst](uint32_t pos, uint8_t b) { dst[pos] = b; };
+        pbft::rp_write_text(put, view, timestamp[i], pid, res, res_len[i], replica, sw);
+      } else {
+        rc = PBFT_EINVAL;  // (no room: keep counting the length)
+      }
+    } else {
+      if (status) status[i] = PBFT_REPLY_GENERAL;
+      const bool room = out && off <= cap;
+      Out o{room ? (char*)out + off : nullptr, room ? cap - off : 0};
+      o.puts("{\"view\":");
+      o.u64(view);
+      o.puts(",\"timestamp\":");
+      o.u64(timestamp[i]);
+      o.puts(",\"peer_id\":\"");
+      for (uint32_t k = 0; k < pbft::RP_PEER_ID_B58; ++k) o.put((char)pid[k]);
+      o.puts("\",\"result\":");
+      o.str((const char*)res, res_len[i]);
+      o.puts(",\"replica\":");
+      o.u64(replica);
+      o.puts(",\"signature\":");
+      o.hex(sg, 64);
+      o.put('}');
+      tl = o.n;
+      if (!room || o.n > o.cap) rc = PBFT_EINVAL;
+    }
+    off += tl;
+  }
+  if (reply_off) reply_off[N] = off;
+  *len = off;
+  return query ? 0 : rc;
+}
+
+int pbft_wire_decode_reply(const uint8_t* text, size_t len, pbft_reply_head* out) {
+  if (!text || !out) return PBFT_EINVAL;
+  memset(out, 0, sizeof *out);
+  pbft::rp_head h;
+  if (pbft::rp_match(text, len, h) != pbft::RP_RH_OK) return 0;
+  out->view = h.view;
+  out->timestamp = h.timestamp;
+  out->result_off = h.result_off;
+  out->result_len = h.result_len;
+  out->replica = h.replica;
+  out->status = PBFT_RH_OK;
+  memcpy(out->peer_id, h.peer_id, sizeof out->peer_id);
+  memcpy(out->sig, h.sig, 64);
+  return 0;
 }
 
 int pbft_records_pack(const uint8_t* R, const uint8_t* S, const uint16_t* key_idx, const uint8_t* msg,

@@ -42,6 +42,7 @@ using namespace pbft;
 #include "wire_pp_kernels.h"
 #include "egress_kernels.h"
 #include "propose_kernels.h"
+#include "reply_kernels.h"
 // Finish configuration by batch size (signatures per lane, product tree, waves per SIMD), measured on MI355X
 // with the lane-parallel wave inversion (profiles/r03/ab_finish.txt): 131k 0.2115 -> 0.1906 ms (width 2),
 // 262k 0.3628 -> 0.3429 (width 4), 2^20 finish kernel 118.6 -> 91.4 us (width 8, tree, 2 waves per SIMD).
@@ -281,6 +282,13 @@ struct pbft_ctx {
   uint8_t* d_propose_io = nullptr;
   size_t propose_io_cap = 0;  // bytes
   int propose_width = PROPOSE_WIDTH_DEFAULT;
+  // pbft_sign_replies_device: the tile sums (grow-only; pbft_reply_reserve); the blocking form's inputs, outputs and
+  // texts (grow-only); the installed identity's PeerId text (reply_core.h), also at word REPLY_KEY_PEER_ID of d_sign_key
+  uint8_t* d_reply = nullptr;
+  size_t reply_cap = 0;  // bytes
+  uint8_t* d_reply_io = nullptr;
+  size_t reply_io_cap = 0;  // bytes
+  char sign_peer_id[pbft::RP_PEER_ID_B58] = {0};
 };
 
 #ifndef PBFT_ENV_SCHED
@@ -1071,6 +1079,8 @@ int pbft_verify_ctx_destroy(pbft_ctx* c) {
   (void)hipFree(c->d_egress_io);
   (void)hipFree(c->d_propose);
   (void)hipFree(c->d_propose_io);
+  (void)hipFree(c->d_reply);
+  (void)hipFree(c->d_reply_io);
   if (c->h_bitmap) (void)hipHostFree(c->h_bitmap);
   if (c->h_stage) (void)hipHostFree(c->h_stage);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -2958,6 +2968,12 @@ int pbft_sign_set_seed(pbft_ctx* c, const uint8_t* seed, uint32_t replica, uint8
   uint8_t pub[32];
   HIP_TRY(hipMemcpyAsync(pub, c->d_sign_key + 16, 32, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  // the identity's PeerId text for the client replies (reply.hip reads it; base58 is host work, once per seed)
+  if (pbft::rp_peer_id_b58(pub, (uint8_t*)c->sign_peer_id) != pbft::RP_PEER_ID_B58)  // (sign_set stays false)
+    return set_err(PBFT_EINVAL, "peer id text is not 52 characters");
+  HIP_TRY(hipMemcpyAsync(c->d_sign_key + REPLY_KEY_PEER_ID, c->sign_peer_id, pbft::RP_PEER_ID_B58,
+                         hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
   if (pub_out) memcpy(pub_out, pub, 32);
   c->sign_set = true;
   c->sign_replica = replica;
@@ -3172,6 +3188,135 @@ int pbft_sign_preprepares_frames(pbft_ctx* c, const uint8_t* ops, uint64_t ops_b
                                         clients + 64 * i, c->sign_replica, digests + 64 * i, sigs + 64 * i, out + at, fl,
                                         &got, nullptr, nullptr);
       if (rc || got != fl) return set_err(PBFT_EINVAL, "general frame encode");
+    }
+  }
+  return PBFT_OK;
+}
+
+// ---- client replies: results hashed with their clients, the replies signed and written on the device
+// (include/pbft_wire.h; reply.hip) ----
+static int ensure_reply(pbft_ctx* c, uint64_t N) {
+  const size_t bytes = reply_ws_bytes(N ? N : 1);
+  if (bytes <= c->reply_cap) return PBFT_OK;
+  if (c->d_reply) HIP_TRY(hipFree(c->d_reply));  // (waits for the device: an earlier call may still use it)
+  c->d_reply = nullptr;
+  c->reply_cap = 0;
+  if (hipMalloc(&c->d_reply, bytes) != hipSuccess) return set_err(PBFT_ENOMEM, "reply workspace alloc");
+  c->reply_cap = bytes;
+  return PBFT_OK;
+}
+
+int pbft_reply_reserve(pbft_ctx* c, uint64_t max_n) {
+  if (!c) return set_err(PBFT_EINVAL, "null context");
+  if (max_n > pbft::RP_MAX_N) return set_err(PBFT_EINVAL, "more than 2^24 replies");
+  HIP_TRY(hipSetDevice(c->device));
+  return ensure_reply(c, max_n);
+}
+
+int pbft_sign_replies_device(pbft_ctx* c, const uint8_t* d_results, uint64_t results_bytes, const uint64_t* d_res_off,
+                             const uint32_t* d_res_len, const uint64_t* d_timestamp, const uint8_t* d_clients,
+                             uint64_t view, uint64_t N, uint8_t* d_out, uint64_t out_cap, uint64_t* d_reply_off,
+                             uint8_t* d_digests, uint8_t* d_sigs, uint8_t* d_status, void* stream) {
+  if (!c) return set_err(PBFT_EINVAL, "null context");
+  if (!c->sign_set) return set_err(PBFT_EINVAL, "no signing seed (pbft_sign_set_seed)");
+  if (N > pbft::RP_MAX_N) return set_err(PBFT_EINVAL, "more than 2^24 replies");
+  if (!d_reply_off || (results_bytes && !d_results) || (out_cap && !d_out) ||
+      (N && (!d_res_off || !d_res_len || !d_timestamp || !d_clients || !d_digests || !d_sigs || !d_status)))
+    return set_err(PBFT_EINVAL, "bad reply argument");
+  if (((uintptr_t)d_results & 15) || ((uintptr_t)d_res_off & 7) || ((uintptr_t)d_res_len & 3) ||
+      ((uintptr_t)d_timestamp & 7) || ((uintptr_t)d_reply_off & 7) || ((uintptr_t)d_digests & 3) || ((uintptr_t)d_sigs & 3))
+    return set_err(PBFT_EINVAL, "misaligned reply pointer");
+  HIP_TRY(hipSetDevice(c->device));
+  int rc = ensure_reply(c, N);
+  if (rc) return rc;
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  HIP_TRY(launch_reply(d_results, results_bytes, d_res_off, d_res_len, d_timestamp, d_clients, view, N, c->d_sign_key,
+                       c->d_tabB, (uint64_t*)c->d_reply, d_out, out_cap, d_reply_off, d_digests, d_sigs, d_status, st));
+  return PBFT_OK;
+}
+
+int pbft_sign_replies(pbft_ctx* c, const uint8_t* results, uint64_t results_bytes, const uint64_t* res_off,
+                      const uint32_t* res_len, const uint64_t* timestamp, const char* clients, uint64_t view, uint64_t N,
+                      uint8_t* out, size_t cap, size_t* len, uint64_t* reply_off, uint8_t* digests, uint8_t* sigs,
+                      uint8_t* status) {
+  if (!c || !len) return set_err(PBFT_EINVAL, "null reply argument");
+  *len = 0;
+  if (!c->sign_set) return set_err(PBFT_EINVAL, "no signing seed (pbft_sign_set_seed)");
+  if (N > pbft::RP_MAX_N) return set_err(PBFT_EINVAL, "more than 2^24 replies");
+  if ((N && (!res_off || !res_len || !timestamp || !clients)) || (results_bytes && !results) || (cap && !out))
+    return set_err(PBFT_EINVAL, "bad reply argument");
+  if (c->in_flight) return set_err(PBFT_EBUSY, "async batch in flight");
+  for (uint64_t i = 0; i < N; ++i)
+    if (res_len[i] > results_bytes || res_off[i] > results_bytes - res_len[i])
+      return set_err(PBFT_EINVAL, "a result outside results_bytes");
+  // the layout is a function of the results, the timestamps and the replica index: known before anything runs
+  std::vector<uint64_t> h_off(N + 1);
+  std::vector<uint8_t> h_st(N ? N : 1);
+  size_t need = 0;
+  int rc = pbft_wire_encode_replies(N, view, timestamp, results, res_off, res_len, c->sign_replica, nullptr, nullptr,
+                                    nullptr, 0, &need, h_off.data(), h_st.data());
+  if (rc) return set_err(PBFT_EINVAL, "bad reply argument");
+  *len = need;
+  if (reply_off) memcpy(reply_off, h_off.data(), 8 * (size_t)(N + 1));
+  if (status && N) memcpy(status, h_st.data(), N);
+  if (!out && cap == 0) return PBFT_OK;  // the size query
+  if (need > cap) return set_err(PBFT_EINVAL, "output buffer too small for the replies");
+  if (N == 0) return PBFT_OK;
+  uint64_t n_general = 0;
+  size_t dev_bytes = 0;  // the canonical replies' texts: what the device writes
+  for (uint64_t i = 0; i < N; ++i) {
+    if (h_st[i] == PBFT_REPLY_GENERAL) ++n_general;
+    else dev_bytes += (size_t)(h_off[i + 1] - h_off[i]);
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t oOff = up(results_bytes + 16), oLen = oOff + up(8 * (size_t)N), oTs = oLen + up(4 * (size_t)N),
+               oCl = oTs + up(8 * (size_t)N), oF = oCl + up(64 * (size_t)N), oD = oF + up(8 * (size_t)(N + 1)),
+               oS = oD + up(64 * (size_t)N), oSt = oS + up(64 * (size_t)N), oO = oSt + up(N);
+  const size_t total = oO + up(dev_bytes);
+  if (total > c->reply_io_cap) {
+    if (c->d_reply_io) HIP_TRY(hipFree(c->d_reply_io));
+    c->d_reply_io = nullptr;
+    c->reply_io_cap = 0;
+    if (hipMalloc(&c->d_reply_io, total) != hipSuccess) return set_err(PBFT_ENOMEM, "reply buffers alloc");
+    c->reply_io_cap = total;
+  }
+  rc = ensure_reply(c, N);
+  if (rc) return rc;
+  uint8_t* d = c->d_reply_io;
+  if (results_bytes) HIP_TRY(hipMemcpyAsync(d, results, results_bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(d + oOff, res_off, 8 * (size_t)N, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(d + oLen, res_len, 4 * (size_t)N, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(d + oTs, timestamp, 8 * (size_t)N, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(d + oCl, clients, 64 * (size_t)N, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(launch_reply(d, results_bytes, (const uint64_t*)(d + oOff), (const uint32_t*)(d + oLen),
+                       (const uint64_t*)(d + oTs), d + oCl, view, N, c->d_sign_key, c->d_tabB, (uint64_t*)c->d_reply,
+                       d + oO, dev_bytes, (uint64_t*)(d + oF), d + oD, d + oS, d + oSt, c->stream));
+  std::vector<uint8_t> tmp_texts, tmp_s;
+  uint8_t* texts_to = out;  // all canonical: the device's stream is the answer
+  if (n_general) {
+    tmp_texts.resize(dev_bytes ? dev_bytes : 1);
+    texts_to = tmp_texts.data();
+    if (!sigs) { tmp_s.resize(64 * (size_t)N); sigs = tmp_s.data(); }
+  }
+  if (dev_bytes) HIP_TRY(hipMemcpyAsync(texts_to, d + oO, dev_bytes, hipMemcpyDeviceToHost, c->stream));
+  if (digests) HIP_TRY(hipMemcpyAsync(digests, d + oD, 64 * (size_t)N, hipMemcpyDeviceToHost, c->stream));
+  if (sigs) HIP_TRY(hipMemcpyAsync(sigs, d + oS, 64 * (size_t)N, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (n_general) {  // the complete stream, on the host: the device's texts in order, the others from the general encoder
+    size_t from = 0;
+    for (uint64_t i = 0; i < N; ++i) {
+      const size_t at = (size_t)h_off[i], tl = (size_t)(h_off[i + 1] - h_off[i]);
+      if (h_st[i] == PBFT_REPLY_OK) {
+        memcpy(out + at, tmp_texts.data() + from, tl);
+        from += tl;
+        continue;
+      }
+      size_t got = 0;
+      const uint64_t off1 = 0;
+      rc = pbft_wire_encode_replies(1, view, timestamp + i, results + res_off[i], &off1, res_len + i, c->sign_replica,
+                                    c->sign_peer_id, sigs + 64 * i, out + at, tl, &got, nullptr, nullptr);
+      if (rc || got != tl) return set_err(PBFT_EINVAL, "general reply encode");
     }
   }
   return PBFT_OK;

@@ -761,6 +761,40 @@ class GpuBatchVerifier:
             d_clients or None, view, first_seq, n, d_out or None, out_cap, d_frame_off or None, d_digests or None,
             d_sigs or None, d_status or None, stream or None))
 
+    # -- client replies: results hashed with their clients, signed and written on the GPU (include/pbft_wire.h) ----
+    def reply_reserve(self, max_n: int) -> None:
+        """pbft_reply_reserve: pre-size the reply workspace (required before capturing sign_replies_device into a
+        graph)."""
+        check(self._lib.pbft_reply_reserve(self._ctx, max_n))
+
+    def sign_replies(self, view: int, requests):
+        """pbft_sign_replies: `requests` (wire.pack_results' tuple, host) -> (stream, reply_off [N + 1], digests [N][64],
+        sigs [N][64], status [N]): the signed replies' texts back to back, what wire.encode_replies writes for them,
+        under the identity of set_signing_seed."""
+        data, nbytes, offs, lens, ts, cl = requests
+        n = len(lens)
+        need = ctypes.c_size_t()
+        args = (self._ctx, _ptr(data), nbytes, _ptr(offs), _ptr(lens), _ptr(ts), _ptr(cl), view, n)
+        check(self._lib.pbft_sign_replies(*args, None, 0, ctypes.byref(need), None, None, None, None))  # the size query
+        out = np.zeros(max(need.value, 1), dtype=np.uint8)
+        off = np.zeros(n + 1, dtype=np.uint64)
+        dig, sigs = np.zeros((n, 64), dtype=np.uint8), np.zeros((n, 64), dtype=np.uint8)
+        st = np.zeros(max(n, 1), dtype=np.uint8)
+        check(self._lib.pbft_sign_replies(*args, _ptr(out), need.value, ctypes.byref(need), _ptr(off),
+                                          _ptr(dig) if n else None, _ptr(sigs) if n else None, _ptr(st)))
+        return out[:need.value], off, dig, sigs, st[:n]
+
+    def sign_replies_device(self, d_results: int, results_bytes: int, d_res_off: int, d_res_len: int, d_timestamp: int,
+                            d_clients: int, view: int, n: int, d_out: int, out_cap: int, d_reply_off: int,
+                            d_digests: int, d_sigs: int, d_status: int, stream: int = 0) -> None:
+        """pbft_sign_replies_device: enqueue only (raw device pointers): n executed requests -> the canonical replies'
+        texts at d_out (any alignment, at most out_cap bytes, whole replies only), d_reply_off [n + 1] u64, d_digests
+        and d_sigs [n][64], d_status [n]."""
+        check(self._lib.pbft_sign_replies_device(
+            self._ctx, d_results or None, results_bytes, d_res_off or None, d_res_len or None, d_timestamp or None,
+            d_clients or None, view, n, d_out or None, out_cap, d_reply_off or None, d_digests or None, d_sigs or None,
+            d_status or None, stream or None))
+
     def close(self):
         if self._ctx:
             self._lib.pbft_verify_ctx_destroy(self._ctx)

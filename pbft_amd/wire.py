@@ -248,3 +248,102 @@ def encode_preprepares(view: int, first_seq: int, requests, replica: int, digest
     check(lib.pbft_wire_encode_preprepares(*args, d.ctypes.data, s.ctypes.data, out.ctypes.data, need.value,
                                            ctypes.byref(need), off.ctypes.data, st.ctypes.data))
     return out[: need.value], off, st[:n]
+
+
+# ---- client replies (include/pbft_wire.h; text rule: pbft_amd/csrc/reply_core.h) ----
+KIND_REPLY = 3  # PBFT_KIND_REPLY
+REPLY_OK, REPLY_GENERAL, REPLY_STALE, REPLY_NOT_COMMITTED = 0, 1, 2, 3  # PBFT_REPLY_*
+REPLY_RESULT_MAX = 3072
+RH_NONE, RH_OK = 0, 1  # PBFT_RH_*
+# pbft_reply_head (include/pbft_wire.h): what decode_reply answers
+ReplyHead = np.dtype([("view", "<u8"), ("timestamp", "<u8"), ("result_off", "<u4"), ("result_len", "<u4"),
+                      ("replica", "<u4"), ("status", "<u4"), ("peer_id", "S52"), ("sig", "u1", 64), ("pad", "u1", 4)])
+assert ReplyHead.itemsize == 152
+_B58 = b"123456789ABCDEFGHJKLMNPQRSTUVWXYZabcdefghijkmnopqrstuvwxyz"
+_SERDE_SHORT = {0x22: b'\\"', 0x5C: b"\\\\", 0x08: b"\\b", 0x0C: b"\\f", 0x0A: b"\\n", 0x0D: b"\\r", 0x09: b"\\t"}
+
+
+def serde_escape(s: bytes) -> bytes:
+    """The body of a JSON string as serde_json writes it: `"` and `\\` escaped, control characters as \\b \\f \\n \\r
+    \\t or \\u00xx, every other byte (0x7F and UTF-8 sequences included) as it is."""
+    out = bytearray()
+    for c in bytes(s):
+        if c in _SERDE_SHORT:
+            out += _SERDE_SHORT[c]
+        elif c < 0x20:
+            out += b"\\u00%02x" % c
+        else:
+            out.append(c)
+    return bytes(out)
+
+
+def peer_id_b58(pub: bytes) -> bytes:
+    """The PeerId text of an Ed25519 key: base58btc of 00 24 08 01 12 20 | A (a Python model of
+    pbft_peer_id_b58_from_key)."""
+    raw = bytes([0x00, 0x24, 0x08, 0x01, 0x12, 0x20]) + bytes(pub)
+    v, out = int.from_bytes(raw, "big"), bytearray()
+    while v:
+        v, r = divmod(v, 58)
+        out.append(_B58[r])
+    out += b"1" * (len(raw) - len(raw.lstrip(b"\0")))
+    return bytes(out[::-1])
+
+
+def reply_canonical(result: bytes) -> bool:
+    return len(result) <= REPLY_RESULT_MAX and all(0x20 <= c <= 0x7E and c not in (0x22, 0x5C) for c in bytes(result))
+
+
+def reply_text(view: int, timestamp: int, peer_id: bytes, result: bytes, replica: int, sig: bytes) -> bytes:
+    """A Python model of one signed reply's text: the reference's ClientReply serialization (src/message.rs:54-103) in
+    its field order, then "replica" and "signature"."""
+    return b'{"view":%d,"timestamp":%d,"peer_id":"%s","result":"%s","replica":%d,"signature":"%s"}' % (
+        view, timestamp, bytes(peer_id), serde_escape(result), replica, bytes(sig).hex().encode())
+
+
+def client_field(client) -> bytes:
+    """C of the reply digest: the client's 64-byte field with everything from its first NUL on replaced by zeros."""
+    c = client.encode() if isinstance(client, str) else bytes(client)
+    c = c[:64].split(b"\0")[0]
+    return c + bytes(64 - len(c))
+
+
+# Executed requests as the arrays the reply entry points take: pack_requests' tuple, the results in the operations' place.
+pack_results = pack_requests
+
+
+def reply_digests(requests) -> np.ndarray:
+    """pbft_reply_digests: D = Blake2b-512(C | result) per reply, uint8[n][64]."""
+    data, nbytes, offs, lens, _, cl = requests
+    n = len(lens)
+    out = np.zeros((n, 64), np.uint8)
+    check(load().pbft_reply_digests(n, cl.ctypes.data, data.ctypes.data, nbytes, offs.ctypes.data, lens.ctypes.data,
+                                    out.ctypes.data))
+    return out
+
+
+def encode_replies(view: int, requests, replica: int, peer_id: bytes, sigs):
+    """pbft_wire_encode_replies: the signed replies of `requests` (pack_results' tuple) back to back.  Returns (stream
+    uint8, reply_off uint64[n + 1], status uint8[n]: REPLY_OK for the canonical form, REPLY_GENERAL for any other)."""
+    lib = load()
+    data, _, offs, lens, ts, _ = requests
+    n = len(lens)
+    s = np.ascontiguousarray(sigs, np.uint8).reshape(n, 64)
+    pid = np.frombuffer(bytes(peer_id), np.uint8).copy()
+    assert len(pid) == 52
+    need = ctypes.c_size_t()
+    off, st = np.zeros(n + 1, np.uint64), np.zeros(max(n, 1), np.uint8)
+    args = (n, view, ts.ctypes.data, data.ctypes.data, offs.ctypes.data, lens.ctypes.data, replica)
+    check(lib.pbft_wire_encode_replies(*args, None, None, None, 0, ctypes.byref(need), None, None))
+    out = np.zeros(max(1, need.value), np.uint8)
+    check(lib.pbft_wire_encode_replies(*args, pid.ctypes.data, s.ctypes.data, out.ctypes.data, need.value,
+                                       ctypes.byref(need), off.ctypes.data, st.ctypes.data))
+    return out[: need.value], off, st[:n]
+
+
+def decode_reply(text: bytes) -> np.ndarray:
+    """pbft_wire_decode_reply: the canonical-reply matcher for one text.  Returns one ReplyHead record (status RH_OK, or
+    all zero: a general JSON parser decides)."""
+    out = np.zeros(1, ReplyHead)
+    src = ctypes.create_string_buffer(bytes(text), max(1, len(text)))
+    check(load().pbft_wire_decode_reply(src, len(text), out.ctypes.data))
+    return out[0]
