@@ -596,6 +596,116 @@ int pbft_sign_replies(pbft_ctx *ctx, const uint8_t *results, uint64_t results_by
                       uint8_t *out, size_t cap, size_t *len, uint64_t *reply_off, uint8_t *digests, uint8_t *sigs,
                       uint8_t *status);
 
+/* ---- the client's side: signed replies in, f + 1 results out (kernels: pbft_amd/csrc/accept.hip; rule:
+ * accept_core.h) ----
+ * A client acts on a result once f + 1 distinct replicas have sent it matching signed replies.  A batch holds N reply
+ * texts, reply i = bytes [off[i], off[i] + len[i]) of one buffer, raw as they arrive (one per connection, no varint);
+ * clients [n_clients][64] are the client address fields these replies were sent to, in the form pbft_reply_digests takes,
+ * and client_idx[i] names reply i's (NULL: every reply is client 0's).
+ * Replies arrive on unauthenticated connections, so the signer is what the text claims and the signature is the
+ * authentication.  Both claims must name the same installed key: "replica":I must be below the installed key count and
+ * "peer_id" must equal, byte for byte, the 52-character PeerId text of installed key I (a per-context device table
+ * built on the host by pbft_accept_reserve: there is no base58 on the device).
+ * The status of reply i, decided in this order: */
+#define PBFT_ACCEPT_OK 0      /* canonical (exactly pbft_wire_decode_reply -> PBFT_RH_OK), the signer's claim holds and
+                                 client_idx[i] < n_clients                                                             */
+#define PBFT_ACCEPT_EDEFER 1  /* not canonical, or not inside text_bytes (then not read); device forms only           */
+#define PBFT_ACCEPT_ESIGNER 2 /* replica >= the installed key count, or the peer id is not that key's                 */
+#define PBFT_ACCEPT_ECLIENT 3 /* client_idx[i] >= n_clients (decided before any address of the table is formed)       */
+#define PBFT_ACCEPT_EJSON 4   /* pbft_accept_replies only: not a ClientReply with the two signed fields               */
+/* A flag beside PBFT_ACCEPT_OK in the status of a reply pbft_accept_replies settled on the host (status & 0xFF is the
+ * value above): the result between the quotes holds a JSON escape; result_off / result_len give that raw span. */
+#define PBFT_ACCEPT_ESCAPED 0x100
+#define PBFT_ACCEPT_NO_REPLY 0xFFFFFFFFu
+/* An OK reply's record is the 160-byte record above: R | S from the hex, pbft_reply_envelope(view, timestamp, D) with
+ * D = Blake2b-512(C | result), the result hashed where it lies in the text, and key index I.  Every other reply has the
+ * all-zero record with key index 0xFFFF, as the frame decoder marks a frame that is not OK, and all-zero head fields
+ * beside its status.
+ * Two replies match iff their 85-byte kind-3 envelopes are equal: the same view, timestamp, client field and result
+ * bytes.  The view is in the match, so replies of different views do not combine; the reference's view is constant and
+ * view change is out of scope. */
+typedef struct {
+  uint64_t view, timestamp;
+  uint32_t result_off, result_len; /* the result's bytes, counted from the text's first byte */
+  uint32_t replica;
+  uint32_t status; /* PBFT_ACCEPT_* (| PBFT_ACCEPT_ESCAPED) */
+} pbft_accept_head;
+/* One per envelope e < min(n_env[0], env_cap): first = the least reply index i with env_idx[i] == e whose signature
+ * verified (that reply's text holds the result the client reads; PBFT_ACCEPT_NO_REPLY when there is none), count = the
+ * tally's distinct-signer count, client = client_idx[first] (0 without one), accepted = count >= need.  Entries at or
+ * beyond the number of envelopes are zero with first = PBFT_ACCEPT_NO_REPLY. */
+typedef struct {
+  uint64_t view, timestamp;
+  uint32_t first, count, client, accepted;
+} pbft_accept_cert;
+#ifdef __cplusplus
+static_assert(sizeof(pbft_accept_head) == 32 && sizeof(pbft_accept_cert) == 32, "32 bytes each");
+#endif
+
+/* Host, one text, no context and no GPU: the general reader pbft_wire_decode_reply leaves to "a general JSON parser".
+ * A serde-exact parse of the signed ClientReply with pbft_wire_decode_json's tokenizer: any whitespace and field order,
+ * unknown fields ignored, a duplicate field an error, "view", "timestamp" and "replica" by serde's u64 rules (replica
+ * <= 65535), "peer_id" exactly 52 base58 characters, "signature" exactly 128 lowercase hex characters (upper case is
+ * refused, as pbft_wire_decode_json refuses it in a vote's signature), all six fields present, valid UTF-8, nothing
+ * behind the closing brace.  The result's JSON escapes are decoded: its bytes are arena[0, return value).
+ * On a text pbft_wire_decode_reply answers PBFT_RH_OK for, head_out is what that function writes.  On any other text that
+ * parses, status is PBFT_RH_GENERAL and result_off / result_len give the raw span between the result's quotes.
+ * Returns the result's length (>= 0), or PBFT_EINVAL (head_out zeroed) for a text that does not parse, an arena that
+ * is too small (len bytes always suffice) or a null argument. */
+#define PBFT_RH_GENERAL 2
+int pbft_wire_decode_reply_json(const uint8_t *text, size_t len, pbft_reply_head *head_out, char *arena,
+                                size_t arena_cap);
+
+/* Build the context's PeerId table [n_keys][52] from the installed key set (PBFT_ENOKEYS without one) and size the
+ * staging of pbft_accept_replies for max_n replies.  Blocking.  The table follows the key set: after
+ * pbft_verify_set_keys or pbft_verify_update_keys (on this context or one that shares its key set) it is stale, the
+ * device forms below answer PBFT_EINVAL until this function is called again, and pbft_accept_replies rebuilds it
+ * itself.  pbft_verify_revoke_keys leaves it as it is: a revoked slot verifies nothing. */
+int pbft_accept_reserve(pbft_ctx *ctx, uint64_t max_n);
+
+/* Device, enqueue only (one kernel node: no allocation, copy, memset or synchronisation, every loop is bounded, no lane
+ * waits for another block; capturable): reply i -> d_records[i], d_heads[i].  d_text is 16-byte aligned and nothing
+ * outside [d_text, round_up(text_bytes, 16)) is read; no byte outside a reply's own [off, off + len) enters its head,
+ * its record or D.  d_records 16-byte aligned, d_off and d_heads 8, d_len and d_client_idx 4.  PBFT_EINVAL: a null or
+ * misaligned pointer, N > 2^24, text_bytes > 2^31, a stale or missing PeerId table; PBFT_ENOKEYS without a key set; a
+ * refused call has enqueued nothing.  N = 0 enqueues nothing. */
+int pbft_wire_decode_replies_device(pbft_ctx *ctx, const uint8_t *d_text, uint64_t text_bytes, const uint64_t *d_off,
+                                    const uint32_t *d_len, const uint32_t *d_client_idx, const uint8_t *d_clients,
+                                    uint32_t n_clients, uint64_t N, uint8_t *d_records, pbft_accept_head *d_heads,
+                                    void *stream);
+
+/* Replies in, certificates out.  Device, enqueue only, one stream: the decode above; pbft_group_envelopes_device over
+ * d_records in place (envelope at +64, key index at +150, stride 160), which writes d_env_idx [N], d_envelopes
+ * [env_cap][85] and d_n_env [2]; pbft_verify_records_device into d_bitmap; pbft_tally_device with n_signers = the
+ * installed key count into d_signers [env_cap][ceil(n_keys / 64)] and d_count [env_cap]; and the certificates d_certs
+ * [env_cap] (three kernel nodes: an initialising one, not a memset; atomicMin on first; the rest).  After
+ * pbft_verify_reserve(N), pbft_group_reserve(N) and pbft_accept_reserve it does no allocation, copy, memset or
+ * synchronisation and is capturable as a plain chain of kernel nodes.  An env_cap below the number of distinct envelopes
+ * loses the later envelopes' replies (counted in d_n_env[1]) and never miscounts.  PBFT_EINVAL as the decode above and
+ * for need = 0, env_cap = 0 with N > 0, a null or misaligned output; a refused call has enqueued nothing.  N = 0 writes
+ * d_n_env = {0, 0} and zeroes the per-envelope outputs (first = PBFT_ACCEPT_NO_REPLY). */
+int pbft_accept_replies_device(pbft_ctx *ctx, const uint8_t *d_text, uint64_t text_bytes, const uint64_t *d_off,
+                               const uint32_t *d_len, const uint32_t *d_client_idx, const uint8_t *d_clients,
+                               uint32_t n_clients, uint64_t N, uint32_t need, uint8_t *d_records,
+                               pbft_accept_head *d_heads, uint64_t *d_bitmap, uint32_t env_cap, uint32_t *d_env_idx,
+                               uint8_t *d_envelopes, uint32_t *d_n_env, uint64_t *d_signers, uint32_t *d_count,
+                               pbft_accept_cert *d_certs, void *stream);
+
+/* Host, blocking, the complete form.  Texts, index and clients go to the device, the decode runs there and the heads
+ * come back; every PBFT_ACCEPT_EDEFER reply then goes through pbft_wire_decode_reply_json on the host: one that parses
+ * gets the signer's and the client's rule, D from the host's Blake2b over the unescaped result, and its record and head
+ * are patched on the device (PBFT_ACCEPT_OK, with PBFT_ACCEPT_ESCAPED when the raw span holds an escape); any other is
+ * PBFT_ACCEPT_EJSON.  Then group, verify, tally and certify run on the settled records.  No status that comes back is
+ * PBFT_ACCEPT_EDEFER.  Back per reply: bitmap_out [ceil(N / 64)], heads_out [N] and, unless NULL, env_idx_out [N]; per
+ * envelope: envelopes_out [env_cap][85], n_env_out [2], signers_out [env_cap][ceil(n_keys / 64)], count_out [env_cap]
+ * and certs_out [env_cap].  PBFT_EINVAL: a text outside text_bytes, need = 0, env_cap = 0 with N > 0, N > 2^24,
+ * text_bytes > 2^31, a null output; PBFT_ENOKEYS without a key set; PBFT_EBUSY while an async batch is in flight. */
+int pbft_accept_replies(pbft_ctx *ctx, const uint8_t *texts, uint64_t text_bytes, const uint64_t *off,
+                        const uint32_t *len, const uint32_t *client_idx, const char *clients /* [n_clients][64] */,
+                        uint32_t n_clients, uint64_t N, uint32_t need, uint32_t env_cap, uint64_t *bitmap_out,
+                        pbft_accept_head *heads_out, uint32_t *env_idx_out, uint8_t *envelopes_out, uint32_t *n_env_out,
+                        uint64_t *signers_out, uint32_t *count_out, pbft_accept_cert *certs_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -160,6 +160,36 @@ pub struct pbft_reply_head {
     pub sig: [u8; 64],
     pub pad: [u8; 4],
 }
+pub const PBFT_RH_GENERAL: u32 = 2;
+pub const PBFT_ACCEPT_OK: u32 = 0;
+pub const PBFT_ACCEPT_EDEFER: u32 = 1;
+pub const PBFT_ACCEPT_ESIGNER: u32 = 2;
+pub const PBFT_ACCEPT_ECLIENT: u32 = 3;
+pub const PBFT_ACCEPT_EJSON: u32 = 4;
+pub const PBFT_ACCEPT_ESCAPED: u32 = 0x100;
+pub const PBFT_ACCEPT_NO_REPLY: u32 = 0xFFFF_FFFF;
+/// One per reply of the acceptance calls (include/pbft_wire.h pbft_accept_head).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct pbft_accept_head {
+    pub view: u64,
+    pub timestamp: u64,
+    pub result_off: u32,
+    pub result_len: u32,
+    pub replica: u32,
+    pub status: u32,
+}
+/// One per envelope of the acceptance calls (include/pbft_wire.h pbft_accept_cert).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct pbft_accept_cert {
+    pub view: u64,
+    pub timestamp: u64,
+    pub first: u32,
+    pub count: u32,
+    pub client: u32,
+    pub accepted: u32,
+}
 /// Replier override of pbft_replica_set_replier: (user, results, results_bytes, res_off, res_len, timestamp, clients,
 /// view, n, replica, out, cap, len).
 pub type pbft_replier_fn = Option<unsafe extern "C" fn(user: *mut c_void, results: *const u8, results_bytes: u64,
@@ -627,4 +657,22 @@ extern "C" {
     pub fn pbft_replica_set_last_timestamp(r: *mut pbft_replica, timestamp: u64) -> c_int;
     pub fn pbft_replica_last_timestamp(r: *mut pbft_replica, out: *mut u64) -> c_int;
     pub fn pbft_replica_get_reply_stats(r: *mut pbft_replica, out: *mut pbft_replica_reply_stats) -> c_int;
+    pub fn pbft_wire_decode_reply_json(text: *const u8, len: usize, head_out: *mut pbft_reply_head, arena: *mut c_char,
+                                       arena_cap: usize) -> c_int;
+    pub fn pbft_accept_reserve(ctx: *mut pbft_ctx, max_n: u64) -> c_int;
+    pub fn pbft_wire_decode_replies_device(ctx: *mut pbft_ctx, d_text: *const u8, text_bytes: u64, d_off: *const u64,
+                                           d_len: *const u32, d_client_idx: *const u32, d_clients: *const u8,
+                                           n_clients: u32, n: u64, d_records: *mut u8, d_heads: *mut pbft_accept_head,
+                                           stream: *mut c_void) -> c_int;
+    pub fn pbft_accept_replies_device(ctx: *mut pbft_ctx, d_text: *const u8, text_bytes: u64, d_off: *const u64,
+                                      d_len: *const u32, d_client_idx: *const u32, d_clients: *const u8, n_clients: u32,
+                                      n: u64, need: u32, d_records: *mut u8, d_heads: *mut pbft_accept_head,
+                                      d_bitmap: *mut u64, env_cap: u32, d_env_idx: *mut u32, d_envelopes: *mut u8,
+                                      d_n_env: *mut u32, d_signers: *mut u64, d_count: *mut u32,
+                                      d_certs: *mut pbft_accept_cert, stream: *mut c_void) -> c_int;
+    pub fn pbft_accept_replies(ctx: *mut pbft_ctx, texts: *const u8, text_bytes: u64, off: *const u64, len: *const u32,
+                               client_idx: *const u32, clients: *const c_char, n_clients: u32, n: u64, need: u32,
+                               env_cap: u32, bitmap_out: *mut u64, heads_out: *mut pbft_accept_head,
+                               env_idx_out: *mut u32, envelopes_out: *mut u8, n_env_out: *mut u32,
+                               signers_out: *mut u64, count_out: *mut u32, certs_out: *mut pbft_accept_cert) -> c_int;
 }

@@ -540,9 +540,72 @@ impl GpuVerifier {
         out.stream.truncate(len);
         Ok(out)
     }
+    /// The client's side (pbft_accept_replies): signed replies as they arrived, one text each, `client_idx[i]` naming
+    /// the entry of `clients` reply i was sent to -> one certificate per distinct (view, timestamp, client, result),
+    /// `accepted` once `need` (f + 1) distinct installed replicas signed it; `texts[cert.first]` holds the result.
+    /// Texts that are not canonical are settled by the host's serde-exact reader, so no status is PBFT_ACCEPT_EDEFER.
+    pub fn accept_replies(&mut self, texts: &[&[u8]], client_idx: &[u32], clients: &[&str], need: u32,
+                          env_cap: u32) -> Result<Accepted> {
+        if self.inflight.is_some() {
+            return Err(Error { code: ffi::PBFT_EBUSY, message: "one batch in flight per context".into() });
+        }
+        if client_idx.len() != texts.len() {
+            return Err(Error { code: ffi::PBFT_EINVAL, message: "one client index per reply".into() });
+        }
+        let (mut wb, mut wa, mut n_keys) = (0u32, 0u32, 0u32);
+        check(unsafe { ffi::pbft_verify_ctx_info(self.ctx, &mut wb, &mut wa, &mut n_keys) })?;
+        let n = texts.len();
+        let (mut buf, mut off, mut len) = (Vec::new(), Vec::with_capacity(n), Vec::with_capacity(n));
+        for t in texts {
+            off.push(buf.len() as u64);
+            len.push(t.len() as u32);
+            buf.extend_from_slice(t);
+        }
+        let mut fields = vec![0u8; 64 * clients.len()];
+        for (i, c) in clients.iter().enumerate() {
+            let b = c.as_bytes();
+            let k = b.len().min(64);
+            fields[64 * i..64 * i + k].copy_from_slice(&b[..k]);
+        }
+        let words_per_env = (n_keys as usize + 63) / 64;
+        let cap_env = env_cap as usize;
+        let mut bitmap = Bitmap::zeros(n);
+        let mut heads = vec![ffi::pbft_accept_head::default(); n];
+        let mut envelopes = vec![[0u8; 85]; cap_env];
+        let mut n_env = [0u32; 2];
+        let mut tally = Tally { signers: vec![0u64; cap_env * words_per_env], counts: vec![0u32; cap_env],
+                                words_per_env };
+        let mut certs = vec![ffi::pbft_accept_cert::default(); cap_env];
+        check(unsafe {
+            ffi::pbft_accept_replies(self.ctx, buf.as_ptr(), buf.len() as u64, off.as_ptr(), len.as_ptr(),
+                                     client_idx.as_ptr(), fields.as_ptr() as *const c_char, clients.len() as u32,
+                                     n as u64, need, env_cap, bitmap.0.as_mut_ptr(), heads.as_mut_ptr(),
+                                     ptr::null_mut(), envelopes.as_mut_ptr() as *mut u8, n_env.as_mut_ptr(),
+                                     tally.signers.as_mut_ptr(), tally.counts.as_mut_ptr(), certs.as_mut_ptr())
+        })?;
+        let kept = (n_env[0] as usize).min(cap_env);
+        envelopes.truncate(kept);
+        tally.signers.truncate(kept * words_per_env);
+        tally.counts.truncate(kept);
+        certs.truncate(kept);
+        Ok(Accepted { bitmap, heads, envelopes, tally, certs, envelopes_found: n_env[0], rows_lost: n_env[1] })
+    }
     pub fn raw(&self) -> *mut ffi::pbft_ctx {
         self.ctx
     }
+}
+
+/// What accept_replies returns: per reply its head and verify bit; per envelope found (at most env_cap) the envelope,
+/// its signer set and count, and its certificate.
+#[derive(Clone, Debug)]
+pub struct Accepted {
+    pub bitmap: Bitmap,
+    pub heads: Vec<ffi::pbft_accept_head>,
+    pub envelopes: Vec<Envelope>,
+    pub tally: Tally,
+    pub certs: Vec<ffi::pbft_accept_cert>,
+    pub envelopes_found: u32,
+    pub rows_lost: u32,
 }
 
 /// One client request as the primary receives it (the reference's ClientRequest, src/message.rs:174-179).

@@ -40,6 +40,9 @@ EXPORTS = (
     # include/pbft_wire.h, the client replies
     "pbft_reply_digests", "pbft_wire_encode_replies", "pbft_wire_decode_reply", "pbft_reply_reserve",
     "pbft_sign_replies_device", "pbft_sign_replies",
+    # include/pbft_wire.h, the client's side
+    "pbft_wire_decode_reply_json", "pbft_accept_reserve", "pbft_wire_decode_replies_device",
+    "pbft_accept_replies_device", "pbft_accept_replies",
 )
 
 ERRORS = {0: "PBFT_OK", -1: "PBFT_EINVAL", -2: "PBFT_EHIP", -3: "PBFT_ENOKEYS",
@@ -171,6 +174,12 @@ def load() -> ctypes.CDLL:
         "pbft_reply_reserve": (i32, [vp, u64]),
         "pbft_sign_replies_device": (i32, [vp, vp, u64, vp, vp, vp, vp, u64, u64, vp, u64, vp, vp, vp, vp, vp]),
         "pbft_sign_replies": (i32, [vp, vp, u64, vp, vp, vp, vp, u64, u64, vp, ctypes.c_size_t, vp, vp, vp, vp, vp]),
+        "pbft_wire_decode_reply_json": (i32, [vp, ctypes.c_size_t, vp, vp, ctypes.c_size_t]),
+        "pbft_accept_reserve": (i32, [vp, u64]),
+        "pbft_wire_decode_replies_device": (i32, [vp, vp, u64, vp, vp, vp, vp, u32, u64, vp, vp, vp]),
+        "pbft_accept_replies_device": (i32, [vp, vp, u64, vp, vp, vp, vp, u32, u64, u32, vp, vp, vp, u32, vp, vp, vp,
+                                             vp, vp, vp, vp]),
+        "pbft_accept_replies": (i32, [vp, vp, u64, vp, vp, vp, vp, u32, u64, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

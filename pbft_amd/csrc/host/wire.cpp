@@ -951,6 +951,87 @@ int pbft_wire_decode_reply(const uint8_t* text, size_t len, pbft_reply_head* out
   return 0;
 }
 
+// The general reader of a signed ClientReply: parse_body's rules for this struct (src/message.rs:54-103 plus the two
+// signed fields).  The result goes to the arena's first bytes; the peer id must be 52 base58 characters and the signature
+// 128 lowercase hex characters once their escapes, if any, are decoded.
+int pbft_wire_decode_reply_json(const uint8_t* text, size_t len, pbft_reply_head* out, char* arena, size_t arena_cap) {
+  if (!text || !out || (!arena && arena_cap)) return PBFT_EINVAL;
+  memset(out, 0, sizeof *out);
+  pbft::rp_head h;
+  if (pbft::rp_match(text, len, h) == pbft::RP_RH_OK) {  // the canonical text: the matcher's fields
+    if (arena_cap < h.result_len) return PBFT_EINVAL;
+    pbft_wire_decode_reply(text, len, out);
+    if (h.result_len) memcpy(arena, text + h.result_off, h.result_len);
+    return (int)h.result_len;
+  }
+  if (len > (size_t)0x7fffffff || !utf8_valid(text, len)) return PBFT_EINVAL;
+  const char* const s0 = (const char*)text;
+  Parser P{s0, s0 + len, arena, arena_cap};
+  if (!P.lit('{')) return PBFT_EINVAL;
+  bool has_v = false, has_t = false, has_p = false, has_res = false, has_r = false, has_s = false;
+  pbft_reply_head r;
+  memset(&r, 0, sizeof r);
+  size_t res_n = 0;
+  // a short string in place or, escaped, unescaped into a buffer of its own (the arena holds the result and nothing else)
+  char sbuf[160];
+  auto private_str = [&](const char** s, size_t* n) {
+    char* const a = P.arena;
+    const size_t c = P.cap, u = P.used;
+    P.arena = sbuf; P.cap = sizeof sbuf; P.used = 0;
+    const bool ok = P.view(s, n);
+    P.arena = a; P.cap = c; P.used = u;
+    return ok;
+  };
+  if (!P.lit('}')) {
+    do {
+      const char* k;
+      const char* s;
+      size_t kn, n;
+      if (!P.key(&k, &kn)) return PBFT_EINVAL;
+      if (eq(k, kn, "view")) {
+        if (has_v || !P.u64(&r.view)) return PBFT_EINVAL;
+        has_v = true;
+      } else if (eq(k, kn, "timestamp")) {
+        if (has_t || !P.u64(&r.timestamp)) return PBFT_EINVAL;
+        has_t = true;
+      } else if (eq(k, kn, "peer_id")) {
+        if (has_p || !private_str(&s, &n) || n != pbft::RP_PEER_ID_B58) return PBFT_EINVAL;
+        for (uint32_t i = 0; i < pbft::RP_PEER_ID_B58; ++i) {
+          if (!pbft::rp_b58_char((uint8_t)s[i])) return PBFT_EINVAL;
+          r.peer_id[i] = s[i];
+        }
+        has_p = true;
+      } else if (eq(k, kn, "result")) {
+        if (has_res) return PBFT_EINVAL;
+        P.ws();
+        const char* const open = P.p;
+        P.used = 0;
+        if (!P.str(&s, &res_n, true)) return PBFT_EINVAL;
+        r.result_off = (uint32_t)(open + 1 - s0);
+        r.result_len = (uint32_t)(P.p - 1 - (open + 1));
+        has_res = true;
+      } else if (eq(k, kn, "replica")) {
+        uint64_t v;
+        if (has_r || !P.u64(&v) || v > 0xFFFFu) return PBFT_EINVAL;
+        r.replica = (uint32_t)v;
+        has_r = true;
+      } else if (eq(k, kn, "signature")) {
+        if (has_s || !private_str(&s, &n) || !parse_hex(s, n, r.sig, 64)) return PBFT_EINVAL;
+        has_s = true;
+      } else if (!P.skip_value()) {
+        return PBFT_EINVAL;
+      }
+    } while (P.lit(','));
+    if (!P.lit('}')) return PBFT_EINVAL;
+  }
+  P.ws();
+  if (P.p != P.e) return PBFT_EINVAL;  // trailing characters: serde_json errors
+  if (!(has_v && has_t && has_p && has_res && has_r && has_s)) return PBFT_EINVAL;
+  r.status = PBFT_RH_GENERAL;
+  *out = r;
+  return (int)res_n;
+}
+
 int pbft_records_pack(const uint8_t* R, const uint8_t* S, const uint16_t* key_idx, const uint8_t* msg,
                       uint32_t msg_stride, uint64_t N, uint8_t* records) {
   if (N && (!R || !S || !key_idx || !msg || !records || msg_stride < PBFT_ENVELOPE_BYTES)) return PBFT_EINVAL;

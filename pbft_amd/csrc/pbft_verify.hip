@@ -43,6 +43,7 @@ using namespace pbft;
 #include "egress_kernels.h"
 #include "propose_kernels.h"
 #include "reply_kernels.h"
+#include "accept_kernels.h"
 // Finish configuration by batch size (signatures per lane, product tree, waves per SIMD), measured on MI355X
 // with the lane-parallel wave inversion (profiles/r03/ab_finish.txt): 131k 0.2115 -> 0.1906 ms (width 2),
 // 262k 0.3628 -> 0.3429 (width 4), 2^20 finish kernel 118.6 -> 91.4 us (width 8, tree, 2 waves per SIMD).
@@ -125,7 +126,12 @@ struct keyset {
   uint32_t cap = 0;      // keys d_keys / d_key_ok hold
   size_t tab_bytes = 0;  // bytes of d_tabA (a later set_keys whose plan's tables fit reuses the buffers)
   int pa = 0;  // positions of the key plan (identifies PLA_HUGE / PLA_BIG / PLA_MID / PLA_SMALL)
+  // the encodings as installed, host side, and a number that changes whenever one of them does: the PeerId table of
+  // pbft_accept_reserve is built from the first and is stale once the second has moved on
+  std::vector<uint8_t> h_keys;
+  uint64_t gen = 0;
 };
+static std::atomic<uint64_t> g_keyset_gen{0};
 static size_t plan_table_words(int pa) {
   return pa == PLA_HUGE::P ? PLA_HUGE::TABLE_WORDS
        : pa == PLA_BIG::P  ? PLA_BIG::TABLE_WORDS
@@ -289,6 +295,15 @@ struct pbft_ctx {
   uint8_t* d_reply_io = nullptr;
   size_t reply_io_cap = 0;  // bytes
   char sign_peer_id[pbft::RP_PEER_ID_B58] = {0};
+  // pbft_accept_reserve: the installed keys' PeerId texts [n_keys][52] and the key set generation they were made from
+  // (0: none); pbft_accept_replies: its staging and the settled replies' patches (grow-only)
+  uint8_t* d_accept_pid = nullptr;
+  uint32_t accept_pid_cap = 0;  // keys
+  uint64_t accept_gen = 0;
+  uint8_t* d_accept_io = nullptr;
+  size_t accept_io_cap = 0;  // bytes
+  uint8_t* d_accept_patch = nullptr;
+  size_t accept_patch_cap = 0;  // bytes
 };
 
 #ifndef PBFT_ENV_SCHED
@@ -1081,6 +1096,9 @@ int pbft_verify_ctx_destroy(pbft_ctx* c) {
   (void)hipFree(c->d_propose_io);
   (void)hipFree(c->d_reply);
   (void)hipFree(c->d_reply_io);
+  (void)hipFree(c->d_accept_pid);
+  (void)hipFree(c->d_accept_io);
+  (void)hipFree(c->d_accept_patch);
   if (c->h_bitmap) (void)hipHostFree(c->h_bitmap);
   if (c->h_stage) (void)hipHostFree(c->h_stage);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -1196,6 +1214,8 @@ int pbft_verify_set_keys(pbft_ctx* c, const uint8_t* A, uint32_t n, uint8_t* key
     c->kstats = ks;
     return rc;
   }
+  k->h_keys.assign(A, A + 32 * (size_t)n);
+  k->gen = ++g_keyset_gen;
   if (k != c->ks) c->adopt(k);
   else c->n_keys = k->n, c->pa = k->pa;  // rebuilt in place: same buffers, new count (and maybe plan)
   ks.table_bytes = k->tab_bytes;
@@ -1266,6 +1286,9 @@ int pbft_verify_update_keys(pbft_ctx* c, const uint32_t* idx, const uint8_t* A, 
   (void)hipStreamSynchronize(c->stream);
   (void)hipFree(d_tmp);
   if (rc) return rc;
+  if (k->h_keys.size() == 32 * (size_t)k->n)
+    for (uint32_t i = 0; i < m; ++i) memcpy(k->h_keys.data() + 32 * (size_t)idx[i], A + 32 * (size_t)i, 32);
+  k->gen = ++g_keyset_gen;
   if (key_ok)
     for (uint32_t i = 0; i < m; ++i) key_ok[i] = ok_all[idx[i]];
   ks.keys_built = m;
@@ -3319,6 +3342,302 @@ int pbft_sign_replies(pbft_ctx* c, const uint8_t* results, uint64_t results_byte
       if (rc || got != tl) return set_err(PBFT_EINVAL, "general reply encode");
     }
   }
+  return PBFT_OK;
+}
+
+// ---- the client's side: signed replies in, certificates out (include/pbft_wire.h; accept.hip; rule: accept_core.h) ----
+static_assert(sizeof(pbft_accept_head) == sizeof(pbft::accept_head) && sizeof(pbft_accept_cert) == sizeof(pbft::accept_cert),
+              "accept.hip writes pbft_accept_head and pbft_accept_cert");
+
+// Device staging of pbft_accept_replies: records | heads | off | len | client_idx | clients | env_idx | envelopes | n_env
+// | signer sets | counts | certs | (16-byte aligned) texts
+struct accept_layout {
+  size_t heads, off, len, ci, cl, idx, env, n_env, set, cnt, cert, text, total;
+  accept_layout(uint64_t N, uint64_t text_bytes, uint32_t n_clients, uint32_t env_cap, uint32_t W) {
+    auto up = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    heads = PBFT_RECORD_BYTES * (size_t)N;
+    off = heads + sizeof(pbft_accept_head) * (size_t)N;
+    len = off + up(8 * (size_t)N);
+    ci = len + up(4 * (size_t)N);
+    cl = ci + up(4 * (size_t)N);
+    idx = cl + up(64 * (size_t)n_clients);
+    env = idx + up(4 * (size_t)N);
+    n_env = env + up((size_t)env_cap * PBFT_ENVELOPE_LEN + 16);
+    set = n_env + 16;
+    cnt = set + up((size_t)env_cap * W * 8);
+    cert = cnt + up((size_t)env_cap * 4);
+    text = cert + up((size_t)env_cap * sizeof(pbft_accept_cert));
+    total = text + up((size_t)text_bytes) + 16;
+  }
+};
+
+static int ensure_accept_io(pbft_ctx* c, size_t bytes) {
+  if (bytes <= c->accept_io_cap) return PBFT_OK;
+  if (c->d_accept_io) HIP_TRY(hipFree(c->d_accept_io));  // (waits for the device: an earlier call may still use it)
+  c->d_accept_io = nullptr;
+  c->accept_io_cap = 0;
+  if (hipMalloc(&c->d_accept_io, bytes) != hipSuccess) return set_err(PBFT_ENOMEM, "accept staging alloc");
+  c->accept_io_cap = bytes;
+  return PBFT_OK;
+}
+
+// The PeerId texts of the installed keys, from the key set's host copy; blocking.
+static int accept_build_table(pbft_ctx* c) {
+  keyset* k = c->ks;
+  if (!k || c->n_keys == 0) return set_err(PBFT_ENOKEYS, "pbft_verify_set_keys not called");
+  if (k->h_keys.size() != 32 * (size_t)k->n) return set_err(PBFT_EINVAL, "the key set holds no host copy of its keys");
+  if (c->accept_gen == k->gen && c->d_accept_pid && c->accept_pid_cap >= k->n) return PBFT_OK;
+  if (c->accept_pid_cap < k->n) {
+    if (c->d_accept_pid) HIP_TRY(hipFree(c->d_accept_pid));
+    c->d_accept_pid = nullptr;
+    c->accept_pid_cap = 0;
+    c->accept_gen = 0;
+    if (hipMalloc(&c->d_accept_pid, (size_t)pbft::RP_PEER_ID_B58 * k->n) != hipSuccess)
+      return set_err(PBFT_ENOMEM, "peer id table alloc");
+    c->accept_pid_cap = k->n;
+  }
+  std::vector<uint8_t> t((size_t)pbft::RP_PEER_ID_B58 * k->n);
+  for (uint32_t i = 0; i < k->n; ++i)
+    if (pbft::rp_peer_id_b58(k->h_keys.data() + 32 * (size_t)i, t.data() + (size_t)pbft::RP_PEER_ID_B58 * i) !=
+        pbft::RP_PEER_ID_B58)
+      return set_err(PBFT_EINVAL, "peer id text");
+  c->accept_gen = 0;
+  HIP_TRY(hipStreamSynchronize(c->stream));  // (no launch of this context still reads the old table)
+  HIP_TRY(hipMemcpy(c->d_accept_pid, t.data(), t.size(), hipMemcpyHostToDevice));
+  c->accept_gen = k->gen;
+  return PBFT_OK;
+}
+
+int pbft_accept_reserve(pbft_ctx* c, uint64_t max_n) {
+  if (!c) return set_err(PBFT_EINVAL, "null context");
+  if (max_n > pbft::AC_MAX_N) return set_err(PBFT_EINVAL, "more than 2^24 replies");
+  if (c->in_flight) return set_err(PBFT_EBUSY, "async batch in flight");
+  HIP_TRY(hipSetDevice(c->device));
+  int rc = accept_build_table(c);
+  if (rc) return rc;
+  // the blocking form's staging for max_n replies of the shortest text, one client and max_n envelopes: a call that
+  // needs more grows it
+  const accept_layout lay(max_n, pbft::RP_TEXT_MIN * max_n, 1, (uint32_t)max_n, tally_words(c->n_keys));
+  return ensure_accept_io(c, lay.total);
+}
+
+static int check_accept_decode_args(pbft_ctx* c, const void* d_text, uint64_t text_bytes, const void* d_off,
+                                    const void* d_len, const void* d_ci, const void* d_clients, uint32_t n_clients,
+                                    uint64_t N, const void* d_records, const void* d_heads) {
+  if (N > pbft::AC_MAX_N) return set_err(PBFT_EINVAL, "more than 2^24 replies");
+  if (text_bytes > pbft::AC_MAX_TEXT_BYTES) return set_err(PBFT_EINVAL, "more than 2^31 bytes of texts");
+  if (N && (!d_off || !d_len || !d_records || !d_heads || (text_bytes && !d_text) || (n_clients && !d_clients)))
+    return set_err(PBFT_EINVAL, "null accept argument");
+  if (((uintptr_t)d_text & 15) || ((uintptr_t)d_off & 7) || ((uintptr_t)d_len & 3) || ((uintptr_t)d_ci & 3) ||
+      ((uintptr_t)d_records & 15) || ((uintptr_t)d_heads & 7))
+    return set_err(PBFT_EINVAL, "misaligned accept pointer");
+  if (c->n_keys == 0 || !c->ks) return set_err(PBFT_ENOKEYS, "pbft_verify_set_keys not called");
+  if (!c->d_accept_pid || c->accept_gen != c->ks->gen || c->accept_pid_cap < c->n_keys)
+    return set_err(PBFT_EINVAL, "no PeerId table for the installed key set: call pbft_accept_reserve");
+  return PBFT_OK;
+}
+
+int pbft_wire_decode_replies_device(pbft_ctx* c, const uint8_t* d_text, uint64_t text_bytes, const uint64_t* d_off,
+                                    const uint32_t* d_len, const uint32_t* d_client_idx, const uint8_t* d_clients,
+                                    uint32_t n_clients, uint64_t N, uint8_t* d_records, pbft_accept_head* d_heads,
+                                    void* stream) {
+  if (!c) return set_err(PBFT_EINVAL, "null context");
+  int rc = check_accept_decode_args(c, d_text, text_bytes, d_off, d_len, d_client_idx, d_clients, n_clients, N,
+                                    d_records, d_heads);
+  if (rc) return rc;
+  if (N == 0) return PBFT_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  HIP_TRY(launch_accept_decode(d_text, text_bytes, d_off, d_len, d_client_idx, d_clients, n_clients, c->d_accept_pid,
+                               c->n_keys, N, d_records, d_heads, st));
+  return PBFT_OK;
+}
+
+// group, verify, tally and certify over N settled records: the back half of both forms
+static int accept_back_half(pbft_ctx* c, const uint32_t* d_client_idx, uint64_t N, uint32_t need, uint8_t* d_records,
+                            uint64_t* dB, uint32_t env_cap, uint32_t* d_env_idx, uint8_t* d_envelopes,
+                            uint32_t* d_n_env, uint64_t* d_signers, uint32_t* d_count, pbft_accept_cert* d_certs,
+                            void* stream) {
+  const uint16_t* const d_key = (const uint16_t*)(d_records + 150);
+  int rc = pbft_group_envelopes_device(c, d_records + 64, PBFT_RECORD_BYTES, d_key, PBFT_RECORD_BYTES, N, env_cap,
+                                       d_env_idx, d_envelopes, d_n_env, stream);
+  if (rc) return rc;
+  if (N) {
+    rc = pbft_verify_records_device(c, d_records, N, dB, stream);
+    if (rc) return rc;
+  }
+  rc = pbft_tally_device(c, dB, d_key, PBFT_RECORD_BYTES, d_env_idx, 4, N, env_cap, c->n_keys, 0, d_signers, d_count,
+                         stream);
+  if (rc) return rc;
+  if (env_cap) {
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    HIP_TRY(launch_accept_certify(dB, d_env_idx, d_client_idx, N, d_envelopes, d_n_env, d_count, env_cap, need, d_certs,
+                                  st));
+  }
+  return PBFT_OK;
+}
+
+int pbft_accept_replies_device(pbft_ctx* c, const uint8_t* d_text, uint64_t text_bytes, const uint64_t* d_off,
+                               const uint32_t* d_len, const uint32_t* d_client_idx, const uint8_t* d_clients,
+                               uint32_t n_clients, uint64_t N, uint32_t need, uint8_t* d_records,
+                               pbft_accept_head* d_heads, uint64_t* dB, uint32_t env_cap, uint32_t* d_env_idx,
+                               uint8_t* d_envelopes, uint32_t* d_n_env, uint64_t* d_signers, uint32_t* d_count,
+                               pbft_accept_cert* d_certs, void* stream) {
+  if (!c) return set_err(PBFT_EINVAL, "null context");
+  // every check of every step first: a refused call has enqueued nothing
+  if (need == 0) return set_err(PBFT_EINVAL, "need is 0");
+  int rc = check_accept_decode_args(c, d_text, text_bytes, d_off, d_len, d_client_idx, d_clients, n_clients, N,
+                                    d_records, d_heads);
+  if (rc) return rc;
+  if (N && !dB) return set_err(PBFT_EINVAL, "null bitmap");
+  if ((uintptr_t)dB & 7) return set_err(PBFT_EINVAL, "misaligned accept pointer");
+  rc = check_group_args(d_records, PBFT_RECORD_BYTES, d_records, PBFT_RECORD_BYTES, N, env_cap, d_env_idx, d_envelopes,
+                        d_n_env);
+  if (rc) return rc;
+  if (env_cap && (!d_signers || !d_count || !d_certs)) return set_err(PBFT_EINVAL, "null accept output");
+  if (((uintptr_t)d_signers & 7) || ((uintptr_t)d_count & 3) || ((uintptr_t)d_certs & 15))
+    return set_err(PBFT_EINVAL, "misaligned accept pointer");
+  if (N) {
+    rc = pbft_wire_decode_replies_device(c, d_text, text_bytes, d_off, d_len, d_client_idx, d_clients, n_clients, N,
+                                         d_records, d_heads, stream);
+    if (rc) return rc;
+  }
+  return accept_back_half(c, d_client_idx, N, need, d_records, dB, env_cap, d_env_idx, d_envelopes, d_n_env, d_signers,
+                          d_count, d_certs, stream);
+}
+
+int pbft_accept_replies(pbft_ctx* c, const uint8_t* texts, uint64_t text_bytes, const uint64_t* off, const uint32_t* len,
+                        const uint32_t* client_idx, const char* clients, uint32_t n_clients, uint64_t N, uint32_t need,
+                        uint32_t env_cap, uint64_t* out, pbft_accept_head* heads_out, uint32_t* env_idx_out,
+                        uint8_t* envelopes_out, uint32_t* n_env_out, uint64_t* signers_out, uint32_t* count_out,
+                        pbft_accept_cert* certs_out) {
+  if (!c) return set_err(PBFT_EINVAL, "null context");
+  if (c->in_flight) return set_err(PBFT_EBUSY, "async batch in flight");
+  if (c->n_keys == 0) return set_err(PBFT_ENOKEYS, "pbft_verify_set_keys not called");
+  if (need == 0) return set_err(PBFT_EINVAL, "need is 0");
+  if (N > pbft::AC_MAX_N) return set_err(PBFT_EINVAL, "more than 2^24 replies");
+  if (text_bytes > pbft::AC_MAX_TEXT_BYTES) return set_err(PBFT_EINVAL, "more than 2^31 bytes of texts");
+  if (N && env_cap == 0) return set_err(PBFT_EINVAL, "env_cap is 0");
+  if (N && (!off || !len || !out || !heads_out || (text_bytes && !texts) || (n_clients && !clients)))
+    return set_err(PBFT_EINVAL, "null accept argument");
+  if (!n_env_out || (env_cap && (!envelopes_out || !signers_out || !count_out || !certs_out)))
+    return set_err(PBFT_EINVAL, "null accept output");
+  for (uint64_t i = 0; i < N; ++i)
+    if (len[i] > text_bytes || off[i] > text_bytes - len[i]) return set_err(PBFT_EINVAL, "a text outside text_bytes");
+  const uint32_t W = tally_words(c->n_keys);
+  const size_t env_bytes = (size_t)env_cap * PBFT_ENVELOPE_LEN, set_bytes = (size_t)env_cap * W * 8,
+               cnt_bytes = (size_t)env_cap * 4, cert_bytes = (size_t)env_cap * sizeof(pbft_accept_cert);
+  if (N == 0) {  // no reply: no envelope, empty sets, no certificate
+    n_env_out[0] = n_env_out[1] = 0;
+    if (env_cap) {
+      memset(envelopes_out, 0, env_bytes);
+      memset(signers_out, 0, set_bytes);
+      memset(count_out, 0, cnt_bytes);
+      memset(certs_out, 0, cert_bytes);
+      for (uint32_t e = 0; e < env_cap; ++e) certs_out[e].first = PBFT_ACCEPT_NO_REPLY;
+    }
+    return PBFT_OK;
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  int rc = accept_build_table(c);  // (blocking anyway: a stale table is rebuilt here)
+  if (rc) return rc;
+  const accept_layout lay(N, text_bytes, n_clients, env_cap, W);
+  rc = ensure_accept_io(c, lay.total);
+  if (rc) return rc;
+  uint8_t* const d = c->d_accept_io;
+  pbft_accept_head* const d_heads = (pbft_accept_head*)(d + lay.heads);
+  const uint32_t* const d_ci = client_idx ? (const uint32_t*)(d + lay.ci) : nullptr;
+  uint64_t* const dB = (uint64_t*)(d + lay.off);  // (the offsets are dead once the decode has run: its words hold the bitmap)
+  if (text_bytes) HIP_TRY(hipMemcpyAsync(d + lay.text, texts, text_bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(d + lay.off, off, 8 * (size_t)N, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(d + lay.len, len, 4 * (size_t)N, hipMemcpyHostToDevice, c->stream));
+  if (client_idx) HIP_TRY(hipMemcpyAsync(d + lay.ci, client_idx, 4 * (size_t)N, hipMemcpyHostToDevice, c->stream));
+  if (n_clients) HIP_TRY(hipMemcpyAsync(d + lay.cl, clients, 64 * (size_t)n_clients, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(launch_accept_decode(d + lay.text, text_bytes, (const uint64_t*)(d + lay.off), (const uint32_t*)(d + lay.len),
+                               d_ci, d + lay.cl, n_clients, c->d_accept_pid, c->n_keys, N, d, d_heads, c->stream));
+  HIP_TRY(hipMemcpyAsync(heads_out, d_heads, sizeof(pbft_accept_head) * (size_t)N, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+
+  // the host's word on every reply the device deferred
+  std::vector<uint32_t> pidx;
+  std::vector<uint8_t> prec;
+  std::vector<pbft_accept_head> phead;
+  std::vector<char> arena;
+  const keyset* const ks = c->ks;
+  for (uint64_t i = 0; i < N; ++i) {
+    pbft_accept_head& h = heads_out[i];
+    if (h.status != PBFT_ACCEPT_EDEFER) continue;
+    h = pbft_accept_head{0, 0, 0, 0, 0, PBFT_ACCEPT_EJSON};
+    if (arena.size() < (size_t)len[i] + 1) arena.resize((size_t)len[i] + 1);
+    pbft_reply_head rh;
+    const int rl = pbft_wire_decode_reply_json(texts + off[i], len[i], &rh, arena.data(), arena.size());
+    if (rl < 0) continue;
+    char pid[pbft::RP_PEER_ID_B58];
+    if (rh.replica >= c->n_keys ||
+        pbft::rp_peer_id_b58(ks->h_keys.data() + 32 * (size_t)rh.replica, (uint8_t*)pid) != pbft::RP_PEER_ID_B58 ||
+        memcmp(pid, rh.peer_id, sizeof pid) != 0) {
+      h.status = PBFT_ACCEPT_ESIGNER;
+      continue;
+    }
+    const uint32_t ci = client_idx ? client_idx[i] : 0;
+    if (ci >= n_clients) {
+      h.status = PBFT_ACCEPT_ECLIENT;
+      continue;
+    }
+    uint8_t D[64], env[PBFT_ENVELOPE_BYTES];
+    const uint64_t o0 = 0;
+    const uint32_t l0 = (uint32_t)rl;
+    if (pbft_reply_digests(1, clients + 64 * (size_t)ci, (const uint8_t*)arena.data(), l0, &o0, &l0, D) != 0)
+      return set_err(PBFT_EINVAL, "reply digest");
+    pbft_reply_envelope(env, rh.view, rh.timestamp, D);
+    const uint16_t key = (uint16_t)rh.replica;
+    prec.resize(prec.size() + PBFT_RECORD_BYTES);
+    pbft_records_pack(rh.sig, rh.sig + 32, &key, env, PBFT_ENVELOPE_BYTES, 1, prec.data() + prec.size() - PBFT_RECORD_BYTES);
+    const bool escaped = memchr(texts + off[i] + rh.result_off, '\\', rh.result_len) != nullptr;
+    h = pbft_accept_head{rh.view, rh.timestamp, rh.result_off, rh.result_len, rh.replica,
+                         PBFT_ACCEPT_OK | (escaped ? (uint32_t)PBFT_ACCEPT_ESCAPED : 0u)};
+    pidx.push_back((uint32_t)i);
+    phead.push_back(h);
+  }
+  std::vector<uint8_t> buf;  // (pageable: it has to outlive the copy, so it lives to the end of the call)
+  if (!pidx.empty()) {  // one H2D copy: indices | records | heads, then a scatter on the device
+    const size_t P = pidx.size();
+    const size_t o_rec = (4 * P + 15) & ~(size_t)15, o_head = o_rec + PBFT_RECORD_BYTES * P;
+    const size_t bytes = o_head + sizeof(pbft_accept_head) * P;
+    if (bytes > c->accept_patch_cap) {
+      if (c->d_accept_patch) HIP_TRY(hipFree(c->d_accept_patch));
+      c->d_accept_patch = nullptr;
+      c->accept_patch_cap = 0;
+      const size_t cap = bytes + (bytes >> 2) + 4096;
+      if (hipMalloc(&c->d_accept_patch, cap) != hipSuccess) return set_err(PBFT_ENOMEM, "accept patch alloc");
+      c->accept_patch_cap = cap;
+    }
+    buf.assign(bytes, 0);
+    memcpy(buf.data(), pidx.data(), 4 * P);
+    memcpy(buf.data() + o_rec, prec.data(), PBFT_RECORD_BYTES * P);
+    memcpy(buf.data() + o_head, phead.data(), sizeof(pbft_accept_head) * P);
+    HIP_TRY(hipMemcpyAsync(c->d_accept_patch, buf.data(), bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(launch_accept_patch((const uint32_t*)c->d_accept_patch, c->d_accept_patch + o_rec,
+                                c->d_accept_patch + o_head, (uint32_t)P, N, d, d_heads, c->stream));
+  }
+  rc = accept_back_half(c, d_ci, N, need, d, dB, env_cap, (uint32_t*)(d + lay.idx), d + lay.env,
+                        (uint32_t*)(d + lay.n_env), (uint64_t*)(d + lay.set), (uint32_t*)(d + lay.cnt),
+                        (pbft_accept_cert*)(d + lay.cert), c->stream);
+  if (rc) {
+    (void)hipStreamSynchronize(c->stream);  // (buf)
+    return rc;
+  }
+  const uint64_t words = (N + 63) / 64;
+  hipError_t e = hipMemcpyAsync(out, dB, words * 8, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess && env_idx_out) e = hipMemcpyAsync(env_idx_out, d + lay.idx, 4 * (size_t)N, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(envelopes_out, d + lay.env, env_bytes, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(n_env_out, d + lay.n_env, 8, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(signers_out, d + lay.set, set_bytes, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(count_out, d + lay.cnt, cnt_bytes, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(certs_out, d + lay.cert, cert_bytes, hipMemcpyDeviceToHost, c->stream);
+  const hipError_t es = hipStreamSynchronize(c->stream);
+  HIP_TRY(e);
+  HIP_TRY(es);
   return PBFT_OK;
 }
 

@@ -187,6 +187,187 @@ def admit_reference(heads, view: int, h: int, log_window: int, n_keys: int, resi
     return dict(cls=cls, counts=counts, clean=clean, res=res, n_res=n_res, keep=keep)
 
 
+_B58_SET = frozenset(b"123456789ABCDEFGHJKLMNPQRSTUVWXYZabcdefghijkmnopqrstuvwxyz")
+_U64 = rb"(0|[1-9][0-9]{0,19})"
+_CANONICAL_REPLY = None
+
+
+def _canonical_reply(text: bytes):
+    """The canonical signed reply (reply_core.h's rp_match) as a regular expression: (view, timestamp, peer_id, result
+    span, replica, signature bytes) or None."""
+    import re
+    global _CANONICAL_REPLY
+    if _CANONICAL_REPLY is None:
+        _CANONICAL_REPLY = re.compile(
+            rb'\{"view":' + _U64 + rb',"timestamp":' + _U64 +
+            rb',"peer_id":"([1-9A-HJ-NP-Za-km-z]{52})","result":"([ !#-\[\]-~]{0,3072})","replica":(0|[1-9][0-9]{0,4})'
+            rb',"signature":"([0-9a-f]{128})"\}')
+    m = _CANONICAL_REPLY.fullmatch(text)
+    if not m:
+        return None
+    view, ts, rep = int(m.group(1)), int(m.group(2)), int(m.group(5))
+    if view >= 2**64 or ts >= 2**64 or rep > 65535:
+        return None
+    return view, ts, m.group(3), m.span(4), rep, bytes.fromhex(m.group(6).decode())
+
+
+def _json_reply(text: bytes):
+    """A signed ClientReply by serde's rules, with `json`: (view, timestamp, peer_id, raw span of the result, replica,
+    signature bytes, result bytes) or None.  (A model for texts a serializer wrote and their variants: it does not
+    chase the corners where Python's reader is laxer than serde's inside unknown fields, such as NaN.)"""
+    import json
+    try:
+        s = text.decode("utf-8")
+
+        def pairs(p):
+            d = dict(p)
+            if len(d) != len(p):
+                raise ValueError("duplicate field")
+            return d
+        j = json.loads(s, object_pairs_hook=pairs)
+    except (ValueError, RecursionError):
+        return None
+    if not isinstance(j, dict) or not {"view", "timestamp", "peer_id", "result", "replica", "signature"} <= set(j):
+        return None
+    for k, top in (("view", 2**64), ("timestamp", 2**64), ("replica", 65536)):
+        if type(j[k]) is not int or not 0 <= j[k] < top:
+            return None
+    if not all(isinstance(j[k], str) for k in ("peer_id", "result", "signature")):
+        return None
+    try:
+        pid, sig, res = j["peer_id"].encode(), j["signature"].encode(), j["result"].encode("utf-8")
+    except UnicodeEncodeError:  # a lone surrogate escape
+        return None
+    if len(pid) != 52 or not set(pid) <= _B58_SET or len(sig) != 128 or not set(sig) <= set(b"0123456789abcdef"):
+        return None
+    # the raw span of the top-level "result": walk the object's members
+    b, i, span = text, text.index(b"{") + 1, None
+
+    def string_end(i):  # i at the opening quote -> the index behind the closing one
+        i += 1
+        while b[i] != 0x22:
+            i += 2 if b[i] == 0x5C else 1
+        return i + 1
+    while True:
+        while b[i] in b" \t\n\r,":
+            i += 1
+        if b[i] == 0x7D:
+            break
+        k0, i = i, string_end(i)
+        key = json.loads(b[k0:i].decode())
+        while b[i] in b" \t\n\r:":
+            i += 1
+        if b[i] == 0x22:
+            v0, i = i, string_end(i)
+            if key == "result":
+                span = (v0 + 1, i - 1)
+        else:
+            depth = 0
+            while True:
+                if b[i] == 0x22:
+                    i = string_end(i)
+                    continue
+                if b[i] in b"{[":
+                    depth += 1
+                elif b[i] in b"}]":
+                    if depth == 0:
+                        break
+                    depth -= 1
+                elif b[i] == 0x2C and depth == 0:
+                    break
+                i += 1
+    return j["view"], j["timestamp"], pid, span, j["replica"], bytes.fromhex(sig.decode()), res
+
+
+def accept_reference(texts, clients, peer_ids, need: int, env_cap: int, verify, client_idx=None, inside=None,
+                     settle: bool = True) -> dict:
+    """The client's acceptance rule (include/pbft_wire.h, pbft_accept_replies) in plain Python, the tests' model.
+    texts: the replies (bytes each); clients: the client address fields (bytes or str, as wire.client_field takes them);
+    peer_ids: the 52-character PeerId text of every installed key, by key index; client_idx: None or one index into
+    `clients` per reply; inside: None or a bool per reply (False: the text does not lie inside text_bytes);
+    verify(replica, sig64, envelope85) -> bool answers for one signature.  settle=True is the blocking form (a text that
+    is not canonical goes through `json`: EJSON or settled), False the device form (such a text is EDEFER).
+    Returns a dict: heads (wire.AcceptHead), sigs (N, 64), env_rows (N, 85; zero unless OK), bits (N,) bool, env_idx,
+    envelopes (env_cap, 85), n_env (2,), signers (env_cap, W) uint64, counts, certs (wire.AcceptCert), results (the
+    result bytes of every OK reply, else None)."""
+    import hashlib
+
+    from .wire import (ACCEPT_ECLIENT, ACCEPT_EDEFER, ACCEPT_EJSON, ACCEPT_ESCAPED, ACCEPT_ESIGNER, ACCEPT_NO_REPLY,
+                       ACCEPT_OK, AcceptCert, AcceptHead, client_field)
+    n, n_keys = len(texts), len(peer_ids)
+    heads = np.zeros(n, AcceptHead)
+    sigs, env_rows = np.zeros((n, 64), np.uint8), np.zeros((n, 85), np.uint8)
+    results = [None] * n
+    for i, t in enumerate(texts):
+        t = bytes(t)
+        heads[i]["status"] = ACCEPT_EDEFER
+        if inside is not None and not inside[i]:
+            continue
+        flag = 0
+        c = _canonical_reply(t)
+        if c is not None:
+            view, ts, pid, span, rep, sig = c
+            res = t[span[0]:span[1]]
+        elif not settle:
+            continue
+        else:
+            g = _json_reply(t)
+            if g is None:
+                heads[i]["status"] = ACCEPT_EJSON
+                continue
+            view, ts, pid, span, rep, sig, res = g
+            flag = ACCEPT_ESCAPED if b"\\" in t[span[0]:span[1]] else 0
+        if rep >= n_keys or bytes(peer_ids[rep]) != pid:
+            heads[i]["status"] = ACCEPT_ESIGNER
+            continue
+        ci = 0 if client_idx is None else int(client_idx[i])
+        if ci >= len(clients):
+            heads[i]["status"] = ACCEPT_ECLIENT
+            continue
+        heads[i] = (view, ts, span[0], span[1] - span[0], rep, ACCEPT_OK | flag)
+        d = hashlib.blake2b(client_field(clients[ci]) + res, digest_size=64).digest()
+        env = b"PBFT\x03" + view.to_bytes(8, "little") + ts.to_bytes(8, "little") + d
+        sigs[i], env_rows[i] = np.frombuffer(sig, np.uint8), np.frombuffer(env, np.uint8)
+        results[i] = res
+    ok = (heads["status"] & 0xFF) == ACCEPT_OK
+    seen: dict = {}
+    env_idx = np.full(n, ENV_NONE, np.uint32)
+    envelopes = np.zeros((env_cap, 85), np.uint8)
+    lost = 0
+    bits = np.zeros(n, bool)
+    W = (n_keys + 63) // 64
+    sets = [set() for _ in range(env_cap)]
+    first = [ACCEPT_NO_REPLY] * env_cap
+    for i in range(n):
+        if not ok[i]:
+            continue
+        rep = int(heads[i]["replica"])
+        bits[i] = bool(verify(rep, sigs[i].tobytes(), env_rows[i].tobytes()))
+        e = seen.setdefault(env_rows[i].tobytes(), len(seen))
+        if e >= env_cap:
+            lost += 1
+            continue
+        env_idx[i], envelopes[e] = e, env_rows[i]
+        if bits[i]:
+            sets[e].add(rep)
+            first[e] = min(first[e], i)
+    signers = np.zeros((env_cap, W), np.uint64)
+    counts = np.zeros(env_cap, np.uint32)
+    certs = np.zeros(env_cap, AcceptCert)
+    certs["first"] = ACCEPT_NO_REPLY
+    for e in range(min(len(seen), env_cap)):
+        for r in sets[e]:
+            signers[e, r // 64] |= np.uint64(1 << (r % 64))
+        counts[e] = len(sets[e])
+        cl = 0 if first[e] == ACCEPT_NO_REPLY or client_idx is None else int(client_idx[first[e]])
+        env = envelopes[e].tobytes()
+        certs[e] = (int.from_bytes(env[5:13], "little"), int.from_bytes(env[13:21], "little"), first[e], len(sets[e]), cl,
+                    int(len(sets[e]) >= need))
+    return dict(heads=heads, sigs=sigs, env_rows=env_rows, bits=bits, env_idx=env_idx, envelopes=envelopes,
+                n_env=np.array([len(seen), lost], np.uint32), signers=signers, counts=counts, certs=certs,
+                results=results)
+
+
 def quorum(counts, need: int) -> np.ndarray:
     """Envelopes with at least `need` distinct valid signers (2f for prepared, 2f + 1 for committed-local:
     src/behavior.rs:177-182, :214-223); bool per envelope."""
@@ -794,6 +975,72 @@ class GpuBatchVerifier:
             self._ctx, d_results or None, results_bytes, d_res_off or None, d_res_len or None, d_timestamp or None,
             d_clients or None, view, n, d_out or None, out_cap, d_reply_off or None, d_digests or None, d_sigs or None,
             d_status or None, stream or None))
+
+    # -- the client's side: signed replies matched, hashed, verified and tallied on the GPU (include/pbft_wire.h) ----
+    def accept_reserve(self, max_n: int) -> None:
+        """pbft_accept_reserve: build the PeerId table of the installed key set and size the blocking form's staging.
+        Needed before the device forms, and again after set_keys / update_keys (with reserve(n) and group_reserve(n)
+        before capturing accept_replies_device into a graph)."""
+        check(self._lib.pbft_accept_reserve(self._ctx, max_n))
+
+    def decode_replies_device(self, d_text: int, text_bytes: int, d_off: int, d_len: int, d_clients: int,
+                              n_clients: int, n: int, d_records: int, d_heads: int, d_client_idx: int = 0,
+                              stream: int = 0) -> None:
+        """pbft_wire_decode_replies_device: enqueue only (raw device pointers; d_text 16-byte aligned): n reply texts ->
+        d_records (n x 160 B) and d_heads (n x 32 B, wire.AcceptHead).  Texts that are not canonical are
+        wire.ACCEPT_EDEFER."""
+        check(self._lib.pbft_wire_decode_replies_device(self._ctx, d_text or None, text_bytes, d_off or None,
+                                                        d_len or None, d_client_idx or None, d_clients or None,
+                                                        n_clients, n, d_records or None, d_heads or None,
+                                                        stream or None))
+
+    def accept_replies_device(self, d_text: int, text_bytes: int, d_off: int, d_len: int, d_clients: int, n_clients: int,
+                              n: int, need: int, d_records: int, d_heads: int, d_bitmap: int, env_cap: int,
+                              d_env_idx: int, d_envelopes: int, d_n_env: int, d_signers: int, d_count: int, d_certs: int,
+                              d_client_idx: int = 0, stream: int = 0) -> None:
+        """pbft_accept_replies_device: decode, group, verify, tally and certify of n replies on one stream; d_certs is
+        [env_cap] wire.AcceptCert."""
+        check(self._lib.pbft_accept_replies_device(
+            self._ctx, d_text or None, text_bytes, d_off or None, d_len or None, d_client_idx or None, d_clients or None,
+            n_clients, n, need, d_records or None, d_heads or None, d_bitmap or None, env_cap, d_env_idx or None,
+            d_envelopes or None, d_n_env or None, d_signers or None, d_count or None, d_certs or None, stream or None))
+
+    def accept_replies(self, texts, clients, need: int, env_cap: int, client_idx=None, text_bytes: int | None = None,
+                       want_env_idx: bool = True) -> dict:
+        """pbft_accept_replies: the blocking, complete form.  texts: wire.pack_replies' tuple (buffer, off, len);
+        clients: the client address fields (bytes or str each, or an (n_clients, 64) uint8 array); client_idx: None or
+        one index per reply.  Returns a dict: bitmap (words), heads (wire.AcceptHead), env_idx or None, envelopes
+        (env_cap, 85), n_env (2,), signers (env_cap, W), counts (env_cap,), certs (wire.AcceptCert): an envelope e with
+        certs[e]["accepted"] is decided, and reply certs[e]["first"] holds its result."""
+        from .wire import AcceptCert, AcceptHead, client_field
+        buf, off, ln = texts
+        buf = np.ascontiguousarray(buf, np.uint8).reshape(-1)
+        off = np.ascontiguousarray(off, np.uint64).reshape(-1)
+        ln = np.ascontiguousarray(ln, np.uint32).reshape(-1)
+        n = len(off)
+        if len(ln) != n:
+            raise ValueError("off and len must have the same length")
+        nbytes = int(ln.sum()) if text_bytes is None else text_bytes
+        if isinstance(clients, np.ndarray):
+            cl = np.ascontiguousarray(clients, np.uint8).reshape(-1, 64)
+        else:
+            cl = np.frombuffer(b"".join(client_field(c) for c in clients), np.uint8).reshape(-1, 64).copy()
+        ci = None
+        if client_idx is not None:
+            ci = np.ascontiguousarray(client_idx, np.uint32).reshape(-1)
+            if len(ci) != n:
+                raise ValueError("client_idx must have one entry per reply")
+        out = dict(bitmap=np.zeros((n + 63) // 64, np.uint64), heads=np.zeros(n, AcceptHead),
+                   env_idx=np.zeros(n, np.uint32) if want_env_idx else None,
+                   envelopes=np.zeros((env_cap, 85), np.uint8), n_env=np.zeros(2, np.uint32),
+                   signers=np.zeros((env_cap, (self.n_keys + 63) // 64), np.uint64), counts=np.zeros(env_cap, np.uint32),
+                   certs=np.zeros(env_cap, AcceptCert))
+        check(self._lib.pbft_accept_replies(
+            self._ctx, _ptr(buf), nbytes, _ptr(off), _ptr(ln), _ptr(ci) if ci is not None else None,
+            _ptr(cl) if len(cl) else None, len(cl), n, need, env_cap, _ptr(out["bitmap"]), _ptr(out["heads"]),
+            _ptr(out["env_idx"]) if want_env_idx else None, _ptr(out["envelopes"]), out["n_env"].ctypes.data,
+            _ptr(out["signers"]), _ptr(out["counts"]), _ptr(out["certs"])))
+        return out
 
     def close(self):
         if self._ctx:

@@ -347,3 +347,44 @@ def decode_reply(text: bytes) -> np.ndarray:
     src = ctypes.create_string_buffer(bytes(text), max(1, len(text)))
     check(load().pbft_wire_decode_reply(src, len(text), out.ctypes.data))
     return out[0]
+
+
+# ---- the client's side: signed replies in, f + 1 results out (include/pbft_wire.h; rule: pbft_amd/csrc/accept_core.h) ----
+ACCEPT_OK, ACCEPT_EDEFER, ACCEPT_ESIGNER, ACCEPT_ECLIENT, ACCEPT_EJSON = range(5)  # PBFT_ACCEPT_*
+ACCEPT_ESCAPED = 0x100   # a flag beside ACCEPT_OK: the raw span [result_off, result_off + result_len) holds an escape
+ACCEPT_NO_REPLY = 0xFFFFFFFF
+RH_GENERAL = 2  # PBFT_RH_GENERAL: decode_reply_json's status for a text that is not canonical
+# pbft_accept_head: one per reply of decode_replies_device / accept_replies
+AcceptHead = np.dtype([("view", "<u8"), ("timestamp", "<u8"), ("result_off", "<u4"), ("result_len", "<u4"),
+                       ("replica", "<u4"), ("status", "<u4")])
+assert AcceptHead.itemsize == 32
+# pbft_accept_cert: one per envelope of accept_replies_device / accept_replies
+AcceptCert = np.dtype([("view", "<u8"), ("timestamp", "<u8"), ("first", "<u4"), ("count", "<u4"), ("client", "<u4"),
+                       ("accepted", "<u4")])
+assert AcceptCert.itemsize == 32
+
+
+def pack_replies(texts):
+    """Reply texts (bytes each) back to back -> (buffer uint8 padded to a multiple of 16, off uint64[n], len
+    uint32[n]): the arrays the acceptance entry points take; the texts' bytes are sum(len)."""
+    lens = np.array([len(t) for t in texts], np.uint32)
+    offs = np.concatenate([[0], np.cumsum(lens, dtype=np.uint64)[:-1]]).astype(np.uint64) if len(texts) else \
+        np.zeros(0, np.uint64)
+    raw = b"".join(bytes(t) for t in texts)
+    buf = np.zeros((len(raw) + 15) // 16 * 16 + 16, np.uint8)
+    buf[:len(raw)] = np.frombuffer(raw, np.uint8)
+    return buf, offs, lens
+
+
+def decode_reply_json(text: bytes):
+    """pbft_wire_decode_reply_json: the serde-exact reader of one signed reply.  Returns (ReplyHead record, result bytes
+    with their escapes decoded), or None for a text that is not a signed ClientReply.  status is RH_OK on a canonical
+    text (the record is decode_reply's) and RH_GENERAL on any other, where result_off / result_len give the raw span
+    between the result's quotes."""
+    out = np.zeros(1, ReplyHead)
+    src = ctypes.create_string_buffer(bytes(text), max(1, len(text)))
+    arena = ctypes.create_string_buffer(max(1, len(text)))
+    rc = load().pbft_wire_decode_reply_json(src, len(text), out.ctypes.data, arena, len(text))
+    if rc < 0:
+        return None
+    return out[0], arena.raw[:rc]
