@@ -1,11 +1,12 @@
 // Client acceptance (include/pbft_wire.h pbft_accept_replies_device): signed replies' texts matched, their results hashed
 // together with their clients and the 160-byte verifier records written on the device; and, behind grouping,
 // verification and tally, one certificate per envelope.  Its own translation unit.  The rule is accept_core.h's; the
-// aligned-dword reader and the Blake2b over C | result are reply.hip's, copied.  Plain HIP C++.
+// aligned-dword reader, the client field's words and the Blake2b over C | result are sign_tile.h's, shared with
+// reply.hip.  Plain HIP C++.
 #include "accept_kernels.h"
 
 #include "../../include/pbft_wire.h"
-#include "digest_kernels.h"
+#include "sign_tile.h"
 
 using namespace pbft;
 
@@ -24,54 +25,6 @@ static constexpr uint32_t AC_HEAD_LOADS = (3 + AC_HEAD_WIN + 3) / 4, AC_TAIL_LOA
 static_assert(AC_HEAD_LOADS <= AC_HEAD_DWORDS && AC_TAIL_LOADS <= AC_TAIL_DWORDS && AC_TAIL_LOADS <= 64, "");
 static_assert(AC_HEAD_DWORDS % 2 == 1 && AC_TAIL_DWORDS % 2 == 1, "odd rows");
 static_assert(RP_TEXT_MIN >= AC_HEAD_WIN + 4 && RP_TEXT_MIN >= AC_TAIL_WIN, "every staged dword holds a byte of the text");
-
-__device__ __forceinline__ uint64_t ac_shfl64(uint64_t v, int src) {
-  const uint32_t lo = __shfl((uint32_t)v, src, 64), hi = __shfl((uint32_t)(v >> 32), src, 64);
-  return ((uint64_t)hi << 32) | lo;
-}
-
-// Bytes [o, o + 4) of the string m[0, len) as a little-endian word, zero past the end, through aligned dwords of which at
-// least one byte belongs to the string (reply.hip's rp_load32).
-__device__ __forceinline__ uint32_t ac_load32(const uint8_t* m, uint64_t len, uint64_t o) {
-  if (o >= len) return 0u;
-  const uintptr_t a = (uintptr_t)(m + o);
-  const uint32_t* q = (const uint32_t*)(a & ~(uintptr_t)3);
-  const uint32_t mis = (uint32_t)(a & 3);
-  const uint32_t lo = q[0];
-  const uint32_t hi = (mis && o + (4 - mis) < len) ? q[1] : 0u;
-  uint32_t w = (uint32_t)((((uint64_t)hi << 32) | lo) >> (8 * mis));
-  const uint64_t rem = len - o;
-  if (rem < 4) w &= (1u << (8 * (uint32_t)rem)) - 1u;
-  return w;
-}
-
-// D = Blake2b-512(C | m[0, len)) as 16 little-endian words (reply.hip's rp_blake2b512).
-__device__ __forceinline__ void ac_blake2b512(uint32_t out[16], const uint64_t cw[8], const uint8_t* m, uint64_t len) {
-  uint64_t h[8] = {0x6a09e667f3bcc908ULL ^ 0x01010040ULL, 0xbb67ae8584caa73bULL, 0x3c6ef372fe94f82bULL,
-                   0xa54ff53a5f1d36f1ULL, 0x510e527fade682d1ULL, 0x9b05688c2b3e6c1fULL,
-                   0x1f83d9abfb41bd6bULL, 0x5be0cd19137e2179ULL};
-  const uint64_t total = RP_CLIENT_FIELD + len;
-  const uint64_t nblocks = (total + 127) / 128;  // (at least one: total >= 64; at most (64 + RP_RESULT_MAX + 127) / 128)
-  for (uint64_t b = 0; b < nblocks; ++b) {
-    uint64_t mw[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      if (b == 0 && j < 8) {
-        mw[j] = cw[j];
-      } else {
-        const uint64_t o = 128 * b + 8 * j - RP_CLIENT_FIELD;
-        mw[j] = ((uint64_t)ac_load32(m, len, o + 4) << 32) | ac_load32(m, len, o);
-      }
-    }
-    const bool last = b == nblocks - 1;
-    blake2b_compress(h, mw, last ? total : 128 * (b + 1), last);
-  }
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    out[2 * i] = (uint32_t)h[i];
-    out[2 * i + 1] = (uint32_t)(h[i] >> 32);
-  }
-}
 
 // Byte k of a text of n bytes from its two LDS rows: k < AC_HEAD_WIN from the head's, k >= n - AC_TAIL_WIN from the tail's
 struct ac_lds_reader {
@@ -123,7 +76,7 @@ __global__ void __launch_bounds__(64) accept_decode_kernel(const uint8_t* __rest
 
   for (int r = 0; r < (int)ACCEPT_TILE; ++r) {
     if (!__shfl((int)cand, r, 64)) continue;  // (wave-uniform)
-    const uint64_t ro = ac_shfl64(o, r);
+    const uint64_t ro = shfl64(o, r);
     const uint64_t re = ro + __shfl(n, r, 64);
     const uint64_t a0 = ro & ~(uint64_t)3, b0 = (re - AC_TAIL_WIN) & ~(uint64_t)3;
     if (lane < (int)AC_HEAD_LOADS) s_head[r][lane] = *(const uint32_t*)(text + a0 + 4 * (uint32_t)lane);
@@ -145,11 +98,11 @@ __global__ void __launch_bounds__(64) accept_decode_kernel(const uint8_t* __rest
   bool res_ok = true;
   for (int r = 0; r < (int)ACCEPT_TILE; ++r) {
     if (!__shfl((int)ok, r, 64)) continue;  // (wave-uniform)
-    const uint8_t* m = text + ac_shfl64(o, r) + __shfl(f.result_off, r, 64);
+    const uint8_t* m = text + shfl64(o, r) + __shfl(f.result_off, r, 64);
     const uint32_t l = __shfl(f.result_len, r, 64);  // (at most RP_RESULT_MAX)
     bool bad = false;
     for (uint32_t k = 4 * (uint32_t)lane; k < l; k += 4 * 64) {
-      const uint32_t w = ac_load32(m, l, k);
+      const uint32_t w = load32_span(m, l, k);
       const uint32_t nb = l - k < 4 ? l - k : 4;
 #pragma unroll
       for (uint32_t b = 0; b < 4; ++b) bad = bad || (b < nb && !pr_alphabet((w >> (8 * b)) & 0xFFu));
@@ -163,23 +116,10 @@ __global__ void __launch_bounds__(64) accept_decode_kernel(const uint8_t* __rest
 
   uint32_t rec[40];
   if (st == AC_OK) {
-    // C: the client field up to its first NUL, zeros behind it
-    const uint8_t* c = clients + (size_t)RP_CLIENT_FIELD * ci;
     uint64_t cw[8];
-    bool open = true;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      uint64_t w = 0;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const uint32_t b = c[8 * j + k];
-        open = open && b != 0;
-        w |= (uint64_t)(open ? b : 0u) << (8 * k);
-      }
-      cw[j] = w;
-    }
+    client_words(cw, clients + (size_t)RP_CLIENT_FIELD * ci);
     uint32_t dg[16];
-    ac_blake2b512(dg, cw, text + o + f.result_off, f.result_len);
+    blake2b512_span<true>(dg, cw, text + o + f.result_off, f.result_len);  // (at most RP_RESULT_MAX / 128 + 1 blocks)
     ac_record(rec, sg, f.view, f.timestamp, dg, f.replica);
   } else {
     ac_record_none(rec);

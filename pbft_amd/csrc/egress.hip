@@ -2,6 +2,7 @@
 // UviBytes/JSON frames on the device, its own translation unit.  The signer's seed is expanded once
 // (egress_seed_kernel); every lane of the signing kernel then does the second half of RFC 8032 signing only.
 #include "egress_kernels.h"
+#include "sign_tile.h"
 #include "verify_kernels.h"
 
 static constexpr uint32_t EG_ENV_DWORDS = 24;  // an envelope's LDS row: 85 bytes, zero-padded to 96
@@ -41,15 +42,6 @@ __global__ void __launch_bounds__(64) egress_seed_kernel(uint32_t* __restrict__ 
   key[EGRESS_KEY_REPLICA] = replica;
 }
 
-__device__ __forceinline__ uint32_t wave_scan_incl(uint32_t v, int lane) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t o = __shfl_up(v, d, 64);
-    if (lane >= d) v += o;
-  }
-  return v;
-}
-
 // Lengths, and their exclusive scan inside each 64-envelope tile (frame_off[i] holds the offset inside the tile
 // until the signing kernel adds the tile's base); sums[t] = tile t's bytes.
 __global__ void __launch_bounds__(256) egress_layout_kernel(const uint8_t* __restrict__ env, uint32_t stride,
@@ -72,25 +64,20 @@ __global__ void __launch_bounds__(256) egress_layout_kernel(const uint8_t* __res
   if (lane == 63 && (i - 63) < N) sums[i >> 6] = incl;
 }
 
-// One wave: sums[t] becomes the bytes in front of tile t; frame_off[N] the total.
-__global__ void __launch_bounds__(64) egress_scan_kernel(uint64_t* __restrict__ sums, uint64_t n_tiles,
-                                                         uint64_t* __restrict__ frame_off, uint64_t N) {
+// One wave, for every caller of launch_tile_scan: sums[t] becomes the bytes in front of tile t; off[N] the total.
+__global__ void __launch_bounds__(64) tile_scan_kernel(uint64_t* __restrict__ sums, uint64_t n_tiles,
+                                                       uint64_t* __restrict__ off, uint64_t N) {
   const int lane = threadIdx.x;
   uint64_t carry = 0;
   for (uint64_t base = 0; base < n_tiles; base += 64) {
     const uint64_t t = base + lane;
-    const uint32_t v = t < n_tiles ? (uint32_t)sums[t] : 0u;  // (a tile's bytes: at most 64 * EG_FRAME_MAX)
+    const uint32_t v = t < n_tiles ? (uint32_t)sums[t] : 0u;  // (a tile's bytes: 64 texts of a few KB each)
     const uint32_t incl = wave_scan_incl(v, lane);
     if (t < n_tiles) sums[t] = carry + (incl - v);
     carry += __shfl(incl, 63, 64);
   }
-  if (lane == 0) frame_off[N] = carry;
+  if (lane == 0) off[N] = carry;
 }
-
-struct eg_lds_sink {
-  uint8_t* p;
-  __device__ __forceinline__ void operator()(uint32_t pos, uint8_t b) const { p[pos] = b; }
-};
 
 // One signature per lane, then the wave's frames.  WPB waves per workgroup; STAGED: the wave assembles its span in LDS
 // and stores it with 16-byte stores (head and tail bytewise), else every lane stores its own frame bytewise.
@@ -142,16 +129,7 @@ __global__ void __launch_bounds__(64 * WPB) egress_sign_kernel(const uint8_t* __
       prefix[j] = key[8 + j];
       A[j] = key[16 + j];
     }
-    uint32_t rh[16], r[8];
-    sha512_pre<32, PBFT_ENVELOPE_LEN>(rh, prefix, m, PBFT_ENVELOPE_LEN);  // r = SHA-512(prefix || M) mod L
-    sc_reduce512(r, rh);
-    ge P;
-    comb_mul_base<PLB>(P, r, tabB);
-    ge_compress_words(R, P);
-    uint32_t kh[16], k[8];
-    sha512_ram<PBFT_ENVELOPE_LEN>(kh, R, A, m, PBFT_ENVELOPE_LEN);  // k = SHA-512(R || A || M) mod L
-    sc_reduce512(k, kh);
-    sc_muladd(S, k, a, r);  // S = (r + k a) mod L
+    sign_expanded<PLB, PBFT_ENVELOPE_LEN>(R, S, a, prefix, A, m, PBFT_ENVELOPE_LEN, tabB);
   }
   if (sigs && live) {
 #pragma unroll
@@ -166,7 +144,7 @@ __global__ void __launch_bounds__(64 * WPB) egress_sign_kernel(const uint8_t* __
     const uint32_t a0 = (uint32_t)((uintptr_t)dst & 15);
     uint8_t* stage = s_stage[wv];
     if (fits) {
-      eg_lds_sink put{stage + a0 + local};
+      lds_sink put{stage + a0 + local};
       eg_write_frame(put, m, replica, R, S);
     }
     uint32_t span = fits ? local + len : 0u;  // the wave's bytes: the end of its last frame that fits
@@ -193,6 +171,10 @@ __global__ void __launch_bounds__(64 * WPB) egress_sign_kernel(const uint8_t* __
   }
 }
 
+void launch_tile_scan(uint64_t* ws, uint64_t n_tiles, uint64_t* d_off, uint64_t N, hipStream_t st) {
+  hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(64), 0, st, ws, n_tiles, d_off, N);
+}
+
 hipError_t launch_egress_seed(uint32_t* d_key, uint32_t replica, const uint32_t* tabB, hipStream_t st) {
   hipLaunchKernelGGL(egress_seed_kernel, dim3(1), dim3(64), 0, st, d_key, replica, tabB);
   return hipGetLastError();
@@ -205,7 +187,7 @@ hipError_t launch_egress(const uint8_t* d_env, uint32_t env_stride, uint64_t N, 
   if (N)
     hipLaunchKernelGGL(egress_layout_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, d_env, env_stride, N,
                        d_key, d_frame_off, ws);
-  hipLaunchKernelGGL(egress_scan_kernel, dim3(1), dim3(64), 0, st, ws, n_tiles, d_frame_off, N);
+  launch_tile_scan(ws, n_tiles, d_frame_off, N, st);
   if (N) {
     uint32_t* sg = (uint32_t*)d_sigs;
 #define PBFT_EGRESS_LAUNCH(WPB_, ST_)                                                                              \

@@ -19,6 +19,10 @@ static inline size_t egress_ws_bytes(uint64_t N) {
 // One lane: SHA-512(seed) -> a, prefix; A = [a]B; key[0..24) and key[EGRESS_KEY_REPLICA] written, the seed zeroed.
 hipError_t launch_egress_seed(uint32_t* d_key, uint32_t replica, const uint32_t* tabB, hipStream_t st);
 
+// The scan over the tiles, for the egress, proposal and reply launchers alike (one wave, one launch on st): ws[t], tile
+// t's bytes, becomes the bytes in front of tile t, and d_off[N] the total.  n_tiles <= EG_MAX_N / EGRESS_TILE; a failed launch shows in the caller's hipGetLastError.
+void launch_tile_scan(uint64_t* ws, uint64_t n_tiles, uint64_t* d_off, uint64_t N, hipStream_t st);
+
 // Three kernel launches on st (lengths and their scan inside each tile, the scan over the tiles, sign and write); no
 // allocation, copy, memset or synchronisation.  N <= EG_MAX_N; N = 0 writes frame_off[0] = 0 with one launch.
 // block: 64 or 256 lanes per workgroup of the signing kernel; direct: every lane stores its own frame bytewise

@@ -10,7 +10,7 @@
 // always has two bytes.  The frame is head | OP | tail: the head is everything in front of OP (at most PR_HEAD_MAX
 // bytes, varint included), the tail everything from `","timestamp":` on (at most PR_TAIL_MAX).
 //
-// The digest on the device: pr_blake2b512 (propose.hip) is Blake2b-512 (digest_kernels.h's compression) over the
+// The digest on the device: blake2b512_span (sign_tile.h) is Blake2b-512 (digest_kernels.h's compression) over the
 // operation where it lies, read through aligned dwords (digest_kernels.h's le64_masked may load the dword behind the
 // operation's last one; this reader does not).  An aligned dword is loaded only if at least one of its four bytes belongs to the operation,
 // and the bytes of it that do not are masked off.  For an operation inside [ops, ops + ops_bytes) with ops 4-byte

@@ -422,6 +422,23 @@ FE_FN void ge_compress_words(uint32_t enc[8], const ge& P) {
   enc[7] |= (xw[0] & 1u) << 31;
 }
 
+// The second half of RFC 8032 signing: M signed under an expanded key, the clamped scalar a, the prefix and the public
+// key's encoding A (8 LE words each).  Outputs the R and S encodings.
+template <class PL, int LEN>
+FE_FN void sign_expanded(uint32_t r_out[8], uint32_t s_out[8], const uint32_t a[8], const uint32_t prefix[8],
+                         const uint32_t A[8], const uint8_t* msg, int len, const uint32_t* tabB) {
+  uint32_t rh[16], r[8];
+  sha512_pre<32, LEN>(rh, prefix, msg, len);        // r = SHA-512(prefix || M) mod L
+  sc_reduce512(r, rh);
+  ge P;
+  comb_mul_base<PL>(P, r, tabB);
+  ge_compress_words(r_out, P);
+  uint32_t kh[16], k[8];
+  sha512_ram<LEN>(kh, r_out, A, msg, len);          // k = SHA-512(R || A || M) mod L
+  sc_reduce512(k, kh);
+  sc_muladd(s_out, k, a, r);                        // S = (r + k*a) mod L
+}
+
 // RFC 8032 Ed25519 signature of M under secret seed (8 LE words).
 // Outputs R and S encodings (8 LE words each) and the public key A.
 template <class PL, int LEN>
@@ -442,15 +459,7 @@ FE_FN void sign_lane(uint32_t r_out[8], uint32_t s_out[8], uint32_t a_out[8], co
   ge P;
   comb_mul_base<PL>(P, ared, tabB);
   ge_compress_words(a_out, P);
-  uint32_t rh[16], r[8];
-  sha512_pre<32, LEN>(rh, prefix, msg, len);        // r = SHA-512(prefix || M) mod L
-  sc_reduce512(r, rh);
-  comb_mul_base<PL>(P, r, tabB);
-  ge_compress_words(r_out, P);
-  uint32_t kh[16], k[8];
-  sha512_ram<LEN>(kh, r_out, a_out, msg, len);      // k = SHA-512(R || A || M) mod L
-  sc_reduce512(k, kh);
-  sc_muladd(s_out, k, a, r);                        // S = (r + k*a) mod L
+  sign_expanded<PL, LEN>(r_out, s_out, a, prefix, a_out, msg, len, tabB);
 }
 
 // Table entry (pos, j) of plan PL for base point P0: j * 2^bitoff(pos) * P0.
