@@ -44,6 +44,7 @@ using namespace pbft;
 #include "propose_kernels.h"
 #include "reply_kernels.h"
 #include "accept_kernels.h"
+#include "sign_host.h"
 // Finish configuration by batch size (signatures per lane, product tree, waves per SIMD), measured on MI355X
 // with the lane-parallel wave inversion (profiles/r03/ab_finish.txt): 131k 0.2115 -> 0.1906 ms (width 2),
 // 262k 0.3628 -> 0.3429 (width 4), 2^20 finish kernel 118.6 -> 91.4 us (width 8, tree, 2 waves per SIMD).
@@ -86,6 +87,18 @@ static int set_err(int code, const char* what) {
       return set_err(PBFT_EHIP, _b);                                                    \
     }                                                                                   \
   } while (0)
+
+// One grow-only device buffer: at least `bytes` afterwards, its contents not kept.  A failed allocation leaves it empty
+// and consistent (null, capacity 0) and returns PBFT_ENOMEM with the caller's text.
+static int grow_device(uint8_t** p, size_t* cap, size_t bytes, const char* what) {
+  if (bytes <= *cap) return PBFT_OK;
+  if (*p) HIP_TRY(hipFree(*p));  // (waits for the device: an earlier call may still use it)
+  *p = nullptr;
+  *cap = 0;
+  if (hipMalloc(p, bytes) != hipSuccess) return set_err(PBFT_ENOMEM, what);
+  *cap = bytes;
+  return PBFT_OK;
+}
 
 // ------------------------------------------------------------------ kernels
 
@@ -270,30 +283,30 @@ struct pbft_ctx {
   uint8_t* d_admit = nullptr;
   size_t admit_cap = 0;  // bytes
   // pbft_sign_set_seed: the expanded signing key a | prefix | A and the replica index (egress_kernels.h), device
-  // resident; pbft_sign_votes_frames_device: the tile sums (grow-only; pbft_egress_reserve); the blocking form's
-  // device buffers (grow-only); the signing kernel's form (PBFT_OPT_EGRESS_BLOCK / _DIRECT)
+  // resident; the signing kernel's form (PBFT_OPT_EGRESS_BLOCK / _DIRECT)
   uint32_t* d_sign_key = nullptr;
   bool sign_set = false;
   uint32_t sign_replica = 0;
-  uint8_t* d_egress = nullptr;
-  size_t egress_cap = 0;  // bytes
-  uint8_t* d_egress_io = nullptr;
-  size_t egress_io_cap = 0;  // bytes
   int egress_block = 64;
   bool egress_direct = false;
-  // pbft_sign_preprepares_frames_device: the tile sums (grow-only; pbft_propose_reserve); the blocking form's requests,
-  // outputs and frames (grow-only)
+  // The tile sums of pbft_sign_votes_frames_device, pbft_sign_preprepares_frames_device and pbft_sign_replies_device
+  // (grow-only; pbft_egress_reserve, pbft_propose_reserve, pbft_reply_reserve).  One each: the device forms run on the
+  // caller's stream, so two of them may be in flight at once.
+  uint8_t* d_egress = nullptr;
+  size_t egress_cap = 0;  // bytes
   uint8_t* d_propose = nullptr;
   size_t propose_cap = 0;  // bytes
-  uint8_t* d_propose_io = nullptr;
-  size_t propose_io_cap = 0;  // bytes
-  int propose_width = PROPOSE_WIDTH_DEFAULT;
-  // pbft_sign_replies_device: the tile sums (grow-only; pbft_reply_reserve); the blocking form's inputs, outputs and
-  // texts (grow-only); the installed identity's PeerId text (reply_core.h), also at word REPLY_KEY_PEER_ID of d_sign_key
   uint8_t* d_reply = nullptr;
   size_t reply_cap = 0;  // bytes
-  uint8_t* d_reply_io = nullptr;
-  size_t reply_io_cap = 0;  // bytes
+  // The device staging of the three blocking forms pbft_sign_votes_frames, pbft_sign_preprepares_frames and
+  // pbft_sign_replies: inputs, outputs and the written bytes (sign_host.h's sign_layout; grow-only).  One for all: each
+  // of them refuses to start while in_flight is set and synchronises `stream` before it returns, so no two hold it at
+  // once (all three use `stream` alone: a call that failed half way is still ordered before the next); the device
+  // forms never touch it.
+  uint8_t* d_sign_io = nullptr;
+  size_t sign_io_cap = 0;  // bytes
+  int propose_width = PROPOSE_WIDTH_DEFAULT;
+  // the installed identity's PeerId text (reply_core.h), also at word REPLY_KEY_PEER_ID of d_sign_key
   char sign_peer_id[pbft::RP_PEER_ID_B58] = {0};
   // pbft_accept_reserve: the installed keys' PeerId texts [n_keys][52] and the key set generation they were made from
   // (0: none); pbft_accept_replies: its staging and the settled replies' patches (grow-only)
@@ -1091,11 +1104,9 @@ int pbft_verify_ctx_destroy(pbft_ctx* c) {
     (void)hipFree(c->d_sign_key);
   }
   (void)hipFree(c->d_egress);
-  (void)hipFree(c->d_egress_io);
   (void)hipFree(c->d_propose);
-  (void)hipFree(c->d_propose_io);
   (void)hipFree(c->d_reply);
-  (void)hipFree(c->d_reply_io);
+  (void)hipFree(c->d_sign_io);
   (void)hipFree(c->d_accept_pid);
   (void)hipFree(c->d_accept_io);
   (void)hipFree(c->d_accept_patch);
@@ -2014,14 +2025,7 @@ int pbft_tally_device(pbft_ctx* c, const uint64_t* dB, const uint16_t* dK, uint3
 
 // ---- envelope grouping (include/pbft_verify.h; kernels: group.hip) ----
 static int ensure_group(pbft_ctx* c, uint64_t N) {
-  const size_t bytes = group_ws_bytes(N);
-  if (bytes <= c->group_cap) return PBFT_OK;
-  if (c->d_group) HIP_TRY(hipFree(c->d_group));  // (waits for the device: an earlier call may still use it)
-  c->d_group = nullptr;
-  c->group_cap = 0;
-  if (hipMalloc(&c->d_group, bytes) != hipSuccess) return set_err(PBFT_ENOMEM, "group workspace alloc");
-  c->group_cap = bytes;
-  return PBFT_OK;
+  return grow_device(&c->d_group, &c->group_cap, group_ws_bytes(N), "group workspace alloc");
 }
 
 static int check_group_args(const void* d_msg, uint32_t msg_stride, const void* dK, uint32_t key_stride, uint64_t N,
@@ -2423,14 +2427,7 @@ static_assert(PBFT_ADMIT_CLEAN == pbft::ADMIT_CLEAN && PBFT_ADMIT_CONTESTED == p
                   PBFT_ADMIT_PAD == pbft::ADMIT_PAD && PBFT_ADMIT_CLASSES == pbft::ADMIT_CLASSES,
               "PBFT_ADMIT_* are admit_core.h's classes");
 static int ensure_admit(pbft_ctx* c, uint64_t plane_bits, uint64_t N) {
-  const size_t bytes = admit_ws(plane_bits, N).total;
-  if (bytes <= c->admit_cap) return PBFT_OK;
-  if (c->d_admit) HIP_TRY(hipFree(c->d_admit));  // (waits for the device: an earlier call may still use it)
-  c->d_admit = nullptr;
-  c->admit_cap = 0;
-  if (hipMalloc(&c->d_admit, bytes) != hipSuccess) return set_err(PBFT_ENOMEM, "admit workspace alloc");
-  c->admit_cap = bytes;
-  return PBFT_OK;
+  return grow_device(&c->d_admit, &c->admit_cap, admit_ws(plane_bits, N).total, "admit workspace alloc");
 }
 
 static int check_admit_shape(uint64_t log_window, uint32_t n_keys, uint64_t N) {
@@ -2477,14 +2474,8 @@ int pbft_admit_reserve(pbft_ctx* c, uint64_t log_window, uint32_t n_keys, uint64
 // ---- connection streams in: the frame index made on the device (include/pbft_wire.h; kernels: wire_index.hip) ----
 static_assert(sizeof(pbft_seg_head) == 24, "pbft_seg_head is 24 bytes");
 static int ensure_index(pbft_ctx* c, uint64_t stream_bytes, uint32_t S) {
-  const size_t bytes = index_ws(stream_bytes, S, c->index_tile).total;
-  if (bytes <= c->index_cap) return PBFT_OK;
-  if (c->d_index) HIP_TRY(hipFree(c->d_index));  // (waits for the device: an earlier call may still use it)
-  c->d_index = nullptr;
-  c->index_cap = 0;
-  if (hipMalloc(&c->d_index, bytes) != hipSuccess) return set_err(PBFT_ENOMEM, "index workspace alloc");
-  c->index_cap = bytes;
-  return PBFT_OK;
+  return grow_device(&c->d_index, &c->index_cap, index_ws(stream_bytes, S, c->index_tile).total,
+                     "index workspace alloc");
 }
 
 static int check_index_args(const void* d_stream, uint64_t stream_bytes, const void* d_seg_off, const void* d_seg_len,
@@ -3004,14 +2995,7 @@ int pbft_sign_set_seed(pbft_ctx* c, const uint8_t* seed, uint32_t replica, uint8
 }
 
 static int ensure_egress(pbft_ctx* c, uint64_t N) {
-  const size_t bytes = egress_ws_bytes(N ? N : 1);
-  if (bytes <= c->egress_cap) return PBFT_OK;
-  if (c->d_egress) HIP_TRY(hipFree(c->d_egress));  // (waits for the device: an earlier call may still use it)
-  c->d_egress = nullptr;
-  c->egress_cap = 0;
-  if (hipMalloc(&c->d_egress, bytes) != hipSuccess) return set_err(PBFT_ENOMEM, "egress workspace alloc");
-  c->egress_cap = bytes;
-  return PBFT_OK;
+  return grow_device(&c->d_egress, &c->egress_cap, egress_ws_bytes(N ? N : 1), "egress workspace alloc");
 }
 
 int pbft_egress_reserve(pbft_ctx* c, uint64_t max_n) {
@@ -3056,27 +3040,61 @@ int pbft_sign_votes_frames(pbft_ctx* c, const uint8_t* envelopes, uint32_t env_s
     return PBFT_OK;
   }
   HIP_TRY(hipSetDevice(c->device));
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t env_bytes = (size_t)env_stride * (N - 1) + pbft::EG_ENV_BYTES;
-  const size_t offF = up(env_bytes), offS = offF + up(8 * (size_t)(N + 1)), offO = offS + up(64 * (size_t)N);
-  const size_t total = offO + up(need);
-  if (total > c->egress_io_cap) {
-    if (c->d_egress_io) HIP_TRY(hipFree(c->d_egress_io));
-    c->d_egress_io = nullptr;
-    c->egress_io_cap = 0;
-    if (hipMalloc(&c->d_egress_io, total) != hipSuccess) return set_err(PBFT_ENOMEM, "egress buffers alloc");
-    c->egress_io_cap = total;
-  }
-  int rc = ensure_egress(c, N);
+  const sign_layout L = sign_votes_layout(env_stride, N, need);
+  int rc = grow_device(&c->d_sign_io, &c->sign_io_cap, L.total, "egress buffers alloc");
   if (rc) return rc;
-  uint8_t* d = c->d_egress_io;
-  HIP_TRY(hipMemcpyAsync(d, envelopes, env_bytes, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(launch_egress(d, env_stride, N, c->d_sign_key, c->d_tabB, (uint64_t*)c->d_egress, d + offO, need,
-                        (uint64_t*)(d + offF), sigs ? d + offS : nullptr, c->egress_block, c->egress_direct,
+  rc = ensure_egress(c, N);
+  if (rc) return rc;
+  uint8_t* d = c->d_sign_io;
+  HIP_TRY(hipMemcpyAsync(d, envelopes, sign_votes_env_bytes(env_stride, N), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(launch_egress(d, env_stride, N, c->d_sign_key, c->d_tabB, (uint64_t*)c->d_egress, d + L.out, need,
+                        (uint64_t*)(d + L.out_off), sigs ? d + L.sig : nullptr, c->egress_block, c->egress_direct,
                         c->stream));
-  if (need) HIP_TRY(hipMemcpyAsync(out, d + offO, need, hipMemcpyDeviceToHost, c->stream));
-  if (frame_off) HIP_TRY(hipMemcpyAsync(frame_off, d + offF, 8 * (size_t)(N + 1), hipMemcpyDeviceToHost, c->stream));
-  if (sigs) HIP_TRY(hipMemcpyAsync(sigs, d + offS, 64 * (size_t)N, hipMemcpyDeviceToHost, c->stream));
+  if (need) HIP_TRY(hipMemcpyAsync(out, d + L.out, need, hipMemcpyDeviceToHost, c->stream));
+  if (frame_off)
+    HIP_TRY(hipMemcpyAsync(frame_off, d + L.out_off, 8 * (size_t)(N + 1), hipMemcpyDeviceToHost, c->stream));
+  if (sigs) HIP_TRY(hipMemcpyAsync(sigs, d + L.sig, 64 * (size_t)N, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return PBFT_OK;
+}
+
+// ---- what the blocking proposal and reply forms share: N items (payload bytes, offsets, lengths, timestamps, clients)
+// up, the device's packed bytes, digests and signatures back, the general items completed on the host (sign_host.h) ----
+static int sign_upload(pbft_ctx* c, const sign_layout& L, const uint8_t* payload, uint64_t payload_bytes,
+                       const uint64_t* off, const uint32_t* len, const uint64_t* timestamp, const char* clients,
+                       uint64_t N) {
+  uint8_t* d = c->d_sign_io;
+  if (payload_bytes) HIP_TRY(hipMemcpyAsync(d, payload, payload_bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(d + L.off, off, 8 * (size_t)N, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(d + L.len, len, 4 * (size_t)N, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(d + L.ts, timestamp, 8 * (size_t)N, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(d + L.cl, clients, 64 * (size_t)N, hipMemcpyHostToDevice, c->stream));
+  return PBFT_OK;
+}
+
+// Where the device's results go on the host.  All items the device's: its packed bytes are the answer and go straight
+// to `out`.  With general items they go to a temporary for the merge, and so does each output the merge reads
+// (signatures; digests too where merge_digests) that the caller left null.
+struct sign_back {
+  std::vector<uint8_t> tmp_stream, tmp_d, tmp_s;
+  uint8_t *stream, *digests, *sigs;
+  sign_back(uint64_t N, const sign_split& s, bool merge_digests, uint8_t* out, uint8_t* digests_, uint8_t* sigs_)
+      : stream(out), digests(digests_), sigs(sigs_) {
+    if (!s.n_general) return;
+    tmp_stream.resize(s.dev_bytes ? s.dev_bytes : 1);
+    stream = tmp_stream.data();
+    if (merge_digests && !digests) { tmp_d.resize(64 * (size_t)N); digests = tmp_d.data(); }
+    if (!sigs) { tmp_s.resize(64 * (size_t)N); sigs = tmp_s.data(); }
+  }
+  sign_back(const sign_back&) = delete;  // (the pointers may be into the temporaries)
+};
+
+// What was asked for, copied back; returns with the stream idle.
+static int sign_read_back(pbft_ctx* c, const sign_layout& L, uint64_t N, size_t dev_bytes, const sign_back& to) {
+  const uint8_t* d = c->d_sign_io;
+  if (dev_bytes) HIP_TRY(hipMemcpyAsync(to.stream, d + L.out, dev_bytes, hipMemcpyDeviceToHost, c->stream));
+  if (to.digests) HIP_TRY(hipMemcpyAsync(to.digests, d + L.dig, 64 * (size_t)N, hipMemcpyDeviceToHost, c->stream));
+  if (to.sigs) HIP_TRY(hipMemcpyAsync(to.sigs, d + L.sig, 64 * (size_t)N, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return PBFT_OK;
 }
@@ -3084,14 +3102,7 @@ int pbft_sign_votes_frames(pbft_ctx* c, const uint8_t* envelopes, uint32_t env_s
 // ---- the primary's proposals: requests hashed, PrePrepares signed and framed on the device (include/pbft_wire.h;
 // propose.hip) ----
 static int ensure_propose(pbft_ctx* c, uint64_t N) {
-  const size_t bytes = propose_ws_bytes(N ? N : 1);
-  if (bytes <= c->propose_cap) return PBFT_OK;
-  if (c->d_propose) HIP_TRY(hipFree(c->d_propose));  // (waits for the device: an earlier call may still use it)
-  c->d_propose = nullptr;
-  c->propose_cap = 0;
-  if (hipMalloc(&c->d_propose, bytes) != hipSuccess) return set_err(PBFT_ENOMEM, "propose workspace alloc");
-  c->propose_cap = bytes;
-  return PBFT_OK;
+  return grow_device(&c->d_propose, &c->propose_cap, propose_ws_bytes(N ? N : 1), "propose workspace alloc");
 }
 
 int pbft_propose_reserve(pbft_ctx* c, uint64_t max_n) {
@@ -3138,9 +3149,7 @@ int pbft_sign_preprepares_frames(pbft_ctx* c, const uint8_t* ops, uint64_t ops_b
     return set_err(PBFT_EINVAL, "bad propose argument");
   if (N && first_seq + (N - 1) < first_seq) return set_err(PBFT_EINVAL, "sequence numbers wrap");
   if (c->in_flight) return set_err(PBFT_EBUSY, "async batch in flight");
-  for (uint64_t i = 0; i < N; ++i)
-    if (op_len[i] > ops_bytes || op_off[i] > ops_bytes - op_len[i])
-      return set_err(PBFT_EINVAL, "an operation outside ops_bytes");
+  if (!sign_spans_inside(op_off, op_len, N, ops_bytes)) return set_err(PBFT_EINVAL, "an operation outside ops_bytes");
   // the layout is a function of the requests and the replica index: known before anything runs
   std::vector<uint64_t> h_off(N + 1);
   std::vector<uint8_t> h_st(N ? N : 1);
@@ -3152,81 +3161,41 @@ int pbft_sign_preprepares_frames(pbft_ctx* c, const uint8_t* ops, uint64_t ops_b
   if (need > cap) return set_err(PBFT_EINVAL, "output buffer too small for the frames");
   if (frame_off) memcpy(frame_off, h_off.data(), 8 * (size_t)(N + 1));
   if (N == 0) return PBFT_OK;
-  uint64_t n_general = 0;
-  size_t dev_bytes = 0;  // the canonical requests' frames: what the device writes
-  for (uint64_t i = 0; i < N; ++i) {
-    if (h_st[i] == PBFT_PROPOSE_GENERAL) ++n_general;
-    else dev_bytes += (size_t)(h_off[i + 1] - h_off[i]);
-  }
+  const sign_split split = sign_count(h_off.data(), h_st.data(), N, PBFT_PROPOSE_OK);  // the device writes the OK ones
   if (status) memcpy(status, h_st.data(), N);
   HIP_TRY(hipSetDevice(c->device));
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t oOff = up(ops_bytes + 16), oLen = oOff + up(8 * (size_t)N), oTs = oLen + up(4 * (size_t)N),
-               oCl = oTs + up(8 * (size_t)N), oF = oCl + up(64 * (size_t)N), oD = oF + up(8 * (size_t)(N + 1)),
-               oS = oD + up(64 * (size_t)N), oSt = oS + up(64 * (size_t)N), oO = oSt + up(N);
-  const size_t total = oO + up(dev_bytes);
-  if (total > c->propose_io_cap) {
-    if (c->d_propose_io) HIP_TRY(hipFree(c->d_propose_io));
-    c->d_propose_io = nullptr;
-    c->propose_io_cap = 0;
-    if (hipMalloc(&c->d_propose_io, total) != hipSuccess) return set_err(PBFT_ENOMEM, "propose buffers alloc");
-    c->propose_io_cap = total;
-  }
+  const sign_layout L(N, ops_bytes, split.dev_bytes);
+  rc = grow_device(&c->d_sign_io, &c->sign_io_cap, L.total, "propose buffers alloc");
+  if (rc) return rc;
   rc = ensure_propose(c, N);
   if (rc) return rc;
-  uint8_t* d = c->d_propose_io;
-  if (ops_bytes) HIP_TRY(hipMemcpyAsync(d, ops, ops_bytes, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(d + oOff, op_off, 8 * (size_t)N, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(d + oLen, op_len, 4 * (size_t)N, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(d + oTs, timestamp, 8 * (size_t)N, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(d + oCl, clients, 64 * (size_t)N, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(launch_propose(d, ops_bytes, (const uint64_t*)(d + oOff), (const uint32_t*)(d + oLen),
-                         (const uint64_t*)(d + oTs), d + oCl, view, first_seq, N, c->d_sign_key, c->d_tabB,
-                         (uint64_t*)c->d_propose, d + oO, dev_bytes, (uint64_t*)(d + oF), d + oD, d + oS, d + oSt,
-                         c->propose_width, c->stream));
-  std::vector<uint8_t> tmp_frames, tmp_d, tmp_s;
-  uint8_t* frames_to = out;  // all canonical: the device's stream is the answer
-  if (n_general) {
-    tmp_frames.resize(dev_bytes ? dev_bytes : 1);
-    frames_to = tmp_frames.data();
-    if (!digests) { tmp_d.resize(64 * (size_t)N); digests = tmp_d.data(); }
-    if (!sigs) { tmp_s.resize(64 * (size_t)N); sigs = tmp_s.data(); }
-  }
-  if (dev_bytes) HIP_TRY(hipMemcpyAsync(frames_to, d + oO, dev_bytes, hipMemcpyDeviceToHost, c->stream));
-  if (digests) HIP_TRY(hipMemcpyAsync(digests, d + oD, 64 * (size_t)N, hipMemcpyDeviceToHost, c->stream));
-  if (sigs) HIP_TRY(hipMemcpyAsync(sigs, d + oS, 64 * (size_t)N, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  if (n_general) {  // the complete stream, on the host: the device's frames in order, the others from the general encoder
-    size_t from = 0;
-    for (uint64_t i = 0; i < N; ++i) {
-      const size_t at = (size_t)h_off[i], fl = (size_t)(h_off[i + 1] - h_off[i]);
-      if (h_st[i] == PBFT_PROPOSE_OK) {
-        memcpy(out + at, tmp_frames.data() + from, fl);
-        from += fl;
-        continue;
-      }
-      size_t got = 0;
-      const uint64_t off1 = 0;
-      rc = pbft_wire_encode_preprepares(1, view, first_seq + i, ops + op_off[i], &off1, op_len + i, timestamp + i,
-                                        clients + 64 * i, c->sign_replica, digests + 64 * i, sigs + 64 * i, out + at, fl,
-                                        &got, nullptr, nullptr);
-      if (rc || got != fl) return set_err(PBFT_EINVAL, "general frame encode");
-    }
-  }
+  rc = sign_upload(c, L, ops, ops_bytes, op_off, op_len, timestamp, clients, N);
+  if (rc) return rc;
+  uint8_t* d = c->d_sign_io;
+  HIP_TRY(launch_propose(d, ops_bytes, (const uint64_t*)(d + L.off), (const uint32_t*)(d + L.len),
+                         (const uint64_t*)(d + L.ts), d + L.cl, view, first_seq, N, c->d_sign_key, c->d_tabB,
+                         (uint64_t*)c->d_propose, d + L.out, split.dev_bytes, (uint64_t*)(d + L.out_off), d + L.dig,
+                         d + L.sig, d + L.st, c->propose_width, c->stream));
+  const sign_back back(N, split, /*merge_digests=*/true, out, digests, sigs);
+  rc = sign_read_back(c, L, N, split.dev_bytes, back);
+  if (rc) return rc;
+  if (!split.n_general) return PBFT_OK;
+  // the complete stream, on the host: the device's frames in order, the others from the general encoder
+  const uint64_t off1 = 0;
+  auto general = [&](uint64_t i, uint8_t* to, size_t fl, size_t* got) {
+    return pbft_wire_encode_preprepares(1, view, first_seq + i, ops + op_off[i], &off1, op_len + i, timestamp + i,
+                                        clients + 64 * i, c->sign_replica, back.digests + 64 * i, back.sigs + 64 * i, to,
+                                        fl, got, nullptr, nullptr);
+  };
+  if (!sign_merge(N, h_off.data(), h_st.data(), PBFT_PROPOSE_OK, back.stream, out, general))
+    return set_err(PBFT_EINVAL, "general frame encode");
   return PBFT_OK;
 }
 
 // ---- client replies: results hashed with their clients, the replies signed and written on the device
 // (include/pbft_wire.h; reply.hip) ----
 static int ensure_reply(pbft_ctx* c, uint64_t N) {
-  const size_t bytes = reply_ws_bytes(N ? N : 1);
-  if (bytes <= c->reply_cap) return PBFT_OK;
-  if (c->d_reply) HIP_TRY(hipFree(c->d_reply));  // (waits for the device: an earlier call may still use it)
-  c->d_reply = nullptr;
-  c->reply_cap = 0;
-  if (hipMalloc(&c->d_reply, bytes) != hipSuccess) return set_err(PBFT_ENOMEM, "reply workspace alloc");
-  c->reply_cap = bytes;
-  return PBFT_OK;
+  return grow_device(&c->d_reply, &c->reply_cap, reply_ws_bytes(N ? N : 1), "reply workspace alloc");
 }
 
 int pbft_reply_reserve(pbft_ctx* c, uint64_t max_n) {
@@ -3269,9 +3238,8 @@ int pbft_sign_replies(pbft_ctx* c, const uint8_t* results, uint64_t results_byte
   if ((N && (!res_off || !res_len || !timestamp || !clients)) || (results_bytes && !results) || (cap && !out))
     return set_err(PBFT_EINVAL, "bad reply argument");
   if (c->in_flight) return set_err(PBFT_EBUSY, "async batch in flight");
-  for (uint64_t i = 0; i < N; ++i)
-    if (res_len[i] > results_bytes || res_off[i] > results_bytes - res_len[i])
-      return set_err(PBFT_EINVAL, "a result outside results_bytes");
+  if (!sign_spans_inside(res_off, res_len, N, results_bytes))
+    return set_err(PBFT_EINVAL, "a result outside results_bytes");
   // the layout is a function of the results, the timestamps and the replica index: known before anything runs
   std::vector<uint64_t> h_off(N + 1);
   std::vector<uint8_t> h_st(N ? N : 1);
@@ -3285,63 +3253,32 @@ int pbft_sign_replies(pbft_ctx* c, const uint8_t* results, uint64_t results_byte
   if (!out && cap == 0) return PBFT_OK;  // the size query
   if (need > cap) return set_err(PBFT_EINVAL, "output buffer too small for the replies");
   if (N == 0) return PBFT_OK;
-  uint64_t n_general = 0;
-  size_t dev_bytes = 0;  // the canonical replies' texts: what the device writes
-  for (uint64_t i = 0; i < N; ++i) {
-    if (h_st[i] == PBFT_REPLY_GENERAL) ++n_general;
-    else dev_bytes += (size_t)(h_off[i + 1] - h_off[i]);
-  }
+  const sign_split split = sign_count(h_off.data(), h_st.data(), N, PBFT_REPLY_OK);  // the device writes the OK ones
   HIP_TRY(hipSetDevice(c->device));
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t oOff = up(results_bytes + 16), oLen = oOff + up(8 * (size_t)N), oTs = oLen + up(4 * (size_t)N),
-               oCl = oTs + up(8 * (size_t)N), oF = oCl + up(64 * (size_t)N), oD = oF + up(8 * (size_t)(N + 1)),
-               oS = oD + up(64 * (size_t)N), oSt = oS + up(64 * (size_t)N), oO = oSt + up(N);
-  const size_t total = oO + up(dev_bytes);
-  if (total > c->reply_io_cap) {
-    if (c->d_reply_io) HIP_TRY(hipFree(c->d_reply_io));
-    c->d_reply_io = nullptr;
-    c->reply_io_cap = 0;
-    if (hipMalloc(&c->d_reply_io, total) != hipSuccess) return set_err(PBFT_ENOMEM, "reply buffers alloc");
-    c->reply_io_cap = total;
-  }
+  const sign_layout L(N, results_bytes, split.dev_bytes);
+  rc = grow_device(&c->d_sign_io, &c->sign_io_cap, L.total, "reply buffers alloc");
+  if (rc) return rc;
   rc = ensure_reply(c, N);
   if (rc) return rc;
-  uint8_t* d = c->d_reply_io;
-  if (results_bytes) HIP_TRY(hipMemcpyAsync(d, results, results_bytes, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(d + oOff, res_off, 8 * (size_t)N, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(d + oLen, res_len, 4 * (size_t)N, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(d + oTs, timestamp, 8 * (size_t)N, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(d + oCl, clients, 64 * (size_t)N, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(launch_reply(d, results_bytes, (const uint64_t*)(d + oOff), (const uint32_t*)(d + oLen),
-                       (const uint64_t*)(d + oTs), d + oCl, view, N, c->d_sign_key, c->d_tabB, (uint64_t*)c->d_reply,
-                       d + oO, dev_bytes, (uint64_t*)(d + oF), d + oD, d + oS, d + oSt, c->stream));
-  std::vector<uint8_t> tmp_texts, tmp_s;
-  uint8_t* texts_to = out;  // all canonical: the device's stream is the answer
-  if (n_general) {
-    tmp_texts.resize(dev_bytes ? dev_bytes : 1);
-    texts_to = tmp_texts.data();
-    if (!sigs) { tmp_s.resize(64 * (size_t)N); sigs = tmp_s.data(); }
-  }
-  if (dev_bytes) HIP_TRY(hipMemcpyAsync(texts_to, d + oO, dev_bytes, hipMemcpyDeviceToHost, c->stream));
-  if (digests) HIP_TRY(hipMemcpyAsync(digests, d + oD, 64 * (size_t)N, hipMemcpyDeviceToHost, c->stream));
-  if (sigs) HIP_TRY(hipMemcpyAsync(sigs, d + oS, 64 * (size_t)N, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  if (n_general) {  // the complete stream, on the host: the device's texts in order, the others from the general encoder
-    size_t from = 0;
-    for (uint64_t i = 0; i < N; ++i) {
-      const size_t at = (size_t)h_off[i], tl = (size_t)(h_off[i + 1] - h_off[i]);
-      if (h_st[i] == PBFT_REPLY_OK) {
-        memcpy(out + at, tmp_texts.data() + from, tl);
-        from += tl;
-        continue;
-      }
-      size_t got = 0;
-      const uint64_t off1 = 0;
-      rc = pbft_wire_encode_replies(1, view, timestamp + i, results + res_off[i], &off1, res_len + i, c->sign_replica,
-                                    c->sign_peer_id, sigs + 64 * i, out + at, tl, &got, nullptr, nullptr);
-      if (rc || got != tl) return set_err(PBFT_EINVAL, "general reply encode");
-    }
-  }
+  rc = sign_upload(c, L, results, results_bytes, res_off, res_len, timestamp, clients, N);
+  if (rc) return rc;
+  uint8_t* d = c->d_sign_io;
+  HIP_TRY(launch_reply(d, results_bytes, (const uint64_t*)(d + L.off), (const uint32_t*)(d + L.len),
+                       (const uint64_t*)(d + L.ts), d + L.cl, view, N, c->d_sign_key, c->d_tabB, (uint64_t*)c->d_reply,
+                       d + L.out, split.dev_bytes, (uint64_t*)(d + L.out_off), d + L.dig, d + L.sig, d + L.st,
+                       c->stream));
+  const sign_back back(N, split, /*merge_digests=*/false, out, digests, sigs);  // (a reply's text holds no digest)
+  rc = sign_read_back(c, L, N, split.dev_bytes, back);
+  if (rc) return rc;
+  if (!split.n_general) return PBFT_OK;
+  // the complete stream, on the host: the device's texts in order, the others from the general encoder
+  const uint64_t off1 = 0;
+  auto general = [&](uint64_t i, uint8_t* to, size_t tl, size_t* got) {
+    return pbft_wire_encode_replies(1, view, timestamp + i, results + res_off[i], &off1, res_len + i, c->sign_replica,
+                                    c->sign_peer_id, back.sigs + 64 * i, to, tl, got, nullptr, nullptr);
+  };
+  if (!sign_merge(N, h_off.data(), h_st.data(), PBFT_REPLY_OK, back.stream, out, general))
+    return set_err(PBFT_EINVAL, "general reply encode");
   return PBFT_OK;
 }
 
@@ -3372,13 +3309,7 @@ struct accept_layout {
 };
 
 static int ensure_accept_io(pbft_ctx* c, size_t bytes) {
-  if (bytes <= c->accept_io_cap) return PBFT_OK;
-  if (c->d_accept_io) HIP_TRY(hipFree(c->d_accept_io));  // (waits for the device: an earlier call may still use it)
-  c->d_accept_io = nullptr;
-  c->accept_io_cap = 0;
-  if (hipMalloc(&c->d_accept_io, bytes) != hipSuccess) return set_err(PBFT_ENOMEM, "accept staging alloc");
-  c->accept_io_cap = bytes;
-  return PBFT_OK;
+  return grow_device(&c->d_accept_io, &c->accept_io_cap, bytes, "accept staging alloc");
 }
 
 // The PeerId texts of the installed keys, from the key set's host copy; blocking.
