@@ -256,6 +256,27 @@ int pbft_verify_batch_device(pbft_ctx *ctx, const uint8_t *d_R, const uint8_t *d
                              const uint8_t *d_msg, uint32_t msg_len, uint32_t msg_stride, uint64_t N,
                              uint64_t *d_bitmap, void *stream);
 
+/* Verification under keys that are NOT installed: every signature carries its public key, A[N][32] raw bytes
+ * (hashed as given), in the place of a key index.  Same semantics as above; a key that does not decompress or is
+ * of small order, like a bad signature, is bit 0, never an error.  Neither form needs a key set (they never
+ * return PBFT_ENOKEYS) and neither reads or disturbs one that is installed.  Each lane decompresses its key and
+ * computes [k](-A) itself (252 doublings, 64 additions), so a signature costs about 14 times what it costs under
+ * an installed key: for clients and peers that have just appeared, not for the replica set.
+ *
+ * Host form: blocking, PCIe copies included; batches above 2^18 signatures go through in chunks.  bitmap_out has
+ * ceil(N/64) words.  PBFT_EBUSY while an async batch is in flight. */
+int pbft_verify_batch_keys(pbft_ctx *ctx, const uint8_t *R, const uint8_t *S, const uint8_t *A /* [N][32] */,
+                           const uint8_t *msg, uint32_t msg_len, uint32_t msg_stride, uint64_t N,
+                           uint64_t *bitmap_out);
+/* Device form: pointers and stream as for pbft_verify_batch_device.  Enqueues two kernels (the sum, the finish)
+ * and nothing else.  d_R / d_S / d_A 16-byte aligned; d_msg must stay readable for N*msg_stride + 16 bytes.
+ * Writes words [0, ceil(N/64)) of d_bitmap (bits >= N are 0) and no other.  It uses the context's workspace:
+ * order it with the context's other launches.  Capturable into a hipGraph after pbft_verify_reserve, as a plain
+ * chain of kernel nodes. */
+int pbft_verify_batch_keys_device(pbft_ctx *ctx, const uint8_t *d_R, const uint8_t *d_S, const uint8_t *d_A,
+                                  const uint8_t *d_msg, uint32_t msg_len, uint32_t msg_stride, uint64_t N,
+                                  uint64_t *d_bitmap, void *stream);
+
 /* Pipelined device form (a stream of rounds): the one-lane-per-signature kernel of this batch runs on
  * `stream`, its batch-inversion finish (which writes d_bitmap) on `finish_stream` after an event, so the
  * next call's kernel on `stream` overlaps this finish and whatever the caller enqueues after it on

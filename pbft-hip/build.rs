@@ -33,7 +33,7 @@ fn main() {
     }
     // HIP kernels + C ABI, gfx950 code objects only (no dual paths, no other targets): one object per
     // source (the four key plans' verify kernels are separate units), then one -shared link
-    let hip_sources = ["pbft_verify.hip", "tables.hip", "finish.hip", "sign.hip", "comb_pa13.hip", "comb_pa14.hip", "comb_pa16.hip", "comb_pa32.hip", "tally.hip", "wire_decode.hip", "group.hip", "wire_index.hip", "admit.hip", "wire_pp.hip", "egress.hip", "propose.hip", "reply.hip", "accept.hip", "debug_arith.hip"];
+    let hip_sources = ["pbft_verify.hip", "tables.hip", "finish.hip", "sign.hip", "comb_pa13.hip", "comb_pa14.hip", "comb_pa16.hip", "comb_pa32.hip", "tally.hip", "wire_decode.hip", "group.hip", "wire_index.hip", "admit.hip", "wire_pp.hip", "egress.hip", "propose.hip", "reply.hip", "accept.hip", "anykey.hip", "debug_arith.hip"];
     for name in hip_sources.iter() {
         let obj = out.join(name.replace(".hip", ".o"));
         run(Command::new(&hipcc)

@@ -421,6 +421,11 @@ extern "C" {
     pub fn pbft_verify_batch_device(ctx: *mut pbft_ctx, d_r: *const u8, d_s: *const u8, d_key_idx: *const u16,
                                     d_msg: *const u8, msg_len: u32, msg_stride: u32, n: u64, d_bitmap: *mut u64,
                                     stream: *mut c_void) -> c_int;
+    pub fn pbft_verify_batch_keys(ctx: *mut pbft_ctx, r: *const u8, s: *const u8, a: *const u8, msg: *const u8,
+                                  msg_len: u32, msg_stride: u32, n: u64, bitmap_out: *mut u64) -> c_int;
+    pub fn pbft_verify_batch_keys_device(ctx: *mut pbft_ctx, d_r: *const u8, d_s: *const u8, d_a: *const u8,
+                                         d_msg: *const u8, msg_len: u32, msg_stride: u32, n: u64,
+                                         d_bitmap: *mut u64, stream: *mut c_void) -> c_int;
     pub fn pbft_verify_batch_device_pipelined(ctx: *mut pbft_ctx, d_r: *const u8, d_s: *const u8,
                                               d_key_idx: *const u16, d_msg: *const u8, msg_len: u32,
                                               msg_stride: u32, n: u64, d_bitmap: *mut u64, stream: *mut c_void,

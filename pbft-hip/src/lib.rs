@@ -446,6 +446,29 @@ impl GpuVerifier {
         })?;
         Ok(ok.into_iter().map(|b| b == 1).collect())
     }
+    /// Verify `(public key, envelope, signature)` triples under keys that are not installed: no `set_keys` first,
+    /// and an installed set is neither read nor disturbed (pbft_verify_batch_keys).  A key that does not decode
+    /// or is of small order is bit 0, like a bad signature.  Blocking.
+    pub fn verify_with_keys(&mut self, items: &[([u8; 32], Envelope, [u8; 64])]) -> Result<Bitmap> {
+        let n = items.len();
+        let mut r = Vec::with_capacity(32 * n);
+        let mut s = Vec::with_capacity(32 * n);
+        let mut a = Vec::with_capacity(32 * n);
+        let mut msg = Vec::with_capacity(ffi::PBFT_ENVELOPE_BYTES * n);
+        for (key, env, sig) in items {
+            r.extend_from_slice(&sig[..32]);
+            s.extend_from_slice(&sig[32..]);
+            a.extend_from_slice(key);
+            msg.extend_from_slice(env);
+        }
+        let mut out = Bitmap::zeros(n);
+        check(unsafe {
+            ffi::pbft_verify_batch_keys(self.ctx, r.as_ptr(), s.as_ptr(), a.as_ptr(), msg.as_ptr(),
+                                        ffi::PBFT_ENVELOPE_BYTES as u32, ffi::PBFT_ENVELOPE_BYTES as u32, n as u64,
+                                        out.0.as_mut_ptr())
+        })?;
+        Ok(out)
+    }
     /// Where the last set_keys / update_keys spent its time.
     pub fn key_stats(&self) -> ffi::pbft_key_stats {
         let mut s = ffi::pbft_key_stats::default();

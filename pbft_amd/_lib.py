@@ -43,6 +43,8 @@ EXPORTS = (
     # include/pbft_wire.h, the client's side
     "pbft_wire_decode_reply_json", "pbft_accept_reserve", "pbft_wire_decode_replies_device",
     "pbft_accept_replies_device", "pbft_accept_replies",
+    # include/pbft_verify.h, uninstalled keys
+    "pbft_verify_batch_keys", "pbft_verify_batch_keys_device",
 )
 
 ERRORS = {0: "PBFT_OK", -1: "PBFT_EINVAL", -2: "PBFT_EHIP", -3: "PBFT_ENOKEYS",
@@ -90,6 +92,9 @@ def load() -> ctypes.CDLL:
         "pbft_verify_poll": (i32, [vp]),
         "pbft_verify_wait": (i32, [vp]),
         "pbft_verify_batch_device": (i32, [vp, vp, vp, vp, vp, u32, u32, u64, vp, vp]),
+        "pbft_verify_batch_keys": (i32, [vp, u8p, u8p, u8p, u8p, u32, u32, u64, vp]),
+        "pbft_verify_batch_keys_device": (i32, [vp, vp, vp, vp, vp, u32, u32, u64, vp, vp]),
+        "pbft_debug_anykey_point": (i32, [vp, u8p, u8p, u8p, u32, u8p, u8p]),  # test hook (not in include/)
         "pbft_verify_reserve": (i32, [vp, u64]),
         "pbft_digest_blake2b512": (i32, [vp, u8p, vp, vp, u64, u8p]),
         "pbft_digest_sha256": (i32, [vp, u8p, vp, vp, u64, u8p]),

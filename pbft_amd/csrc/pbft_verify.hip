@@ -44,6 +44,7 @@ using namespace pbft;
 #include "propose_kernels.h"
 #include "reply_kernels.h"
 #include "accept_kernels.h"
+#include "anykey_kernels.h"
 #include "sign_host.h"
 // Finish configuration by batch size (signatures per lane, product tree, waves per SIMD), measured on MI355X
 // with the lane-parallel wave inversion (profiles/r03/ab_finish.txt): 131k 0.2115 -> 0.1906 ms (width 2),
@@ -592,6 +593,23 @@ static int ensure_work2(pbft_ctx* c, uint64_t N) {
   return PBFT_OK;
 }
 
+// The finish behind a one-lane-per-signature kernel (the comb, or anykey_kernel): signatures per finish lane, product
+// tree and waves per SIMD by batch size (PBFT_FIN_* above).
+static hipError_t launch_finish_by_n(const pbft_ctx* c, const uint8_t* dR, uint32_t rs_stride, const uint32_t* xyz,
+                                     const uint8_t* flags, uint64_t N, uint64_t* dB, hipStream_t st) {
+  const bool big = N >= ((uint64_t)1 << 19);
+  int fm = big ? PBFT_FIN_FM_BIG : N > PBFT_FIN_SMALL_UPTO ? PBFT_FIN_FM_MID
+                                 : N > PBFT_FIN_TINY_UPTO  ? PBFT_FIN_FM_SMALL : 1;
+  // cross-lane product tree (one variable-time inversion per 16-lane row since r04, per wave before) where few
+  // signatures share a lane: 131k 0.2106 -> 0.2061 ms at fm 4, 0.2467 -> 0.2160 at fm 1; no gain at fm 16
+  // (profiles/r02_ab_log.md); lv is a flag here, finish.hip compiles the tree depth (PBFT_FIN_LV)
+  int lv = fm <= PBFT_FIN_TREE_MAX_FM ? PBFT_FIN_LV : 0;
+  if (c->fin_m) fm = c->fin_m;
+  if (c->fin_tree >= 0) lv = c->fin_tree;
+  const int fw = c->fin_waves ? c->fin_waves : (big ? PBFT_FIN_W_BIG : 1);
+  return launch_finish(fm, lv, fw, dR, rs_stride, xyz, flags, N, dB, st);
+}
+
 // fst != null: pipelined form -- the finish runs on fst after an event, on one of two
 // workspace halves, so the next launch's comb (on st) overlaps it.  slot 1: the second workspace (votes chunks
 // on stream2; no timing events, never pipelined).
@@ -644,18 +662,7 @@ static int launch_verify(pbft_ctx* c, const uint8_t* dR, const uint8_t* dS, cons
     st = fst;
   }
   if (!latency_mode) {  // (the latency kernel writes the bitmap itself)
-    // signatures per finish lane, product tree and waves per SIMD by batch size (PBFT_FIN_* above)
-    const bool big = N >= ((uint64_t)1 << 19);
-    int fm = big ? PBFT_FIN_FM_BIG : N > PBFT_FIN_SMALL_UPTO ? PBFT_FIN_FM_MID
-                                   : N > PBFT_FIN_TINY_UPTO  ? PBFT_FIN_FM_SMALL : 1;
-    // cross-lane product tree (one variable-time inversion per 16-lane row since r04, per wave before) where few
-    // signatures share a lane: 131k 0.2106 -> 0.2061 ms at fm 4, 0.2467 -> 0.2160 at fm 1; no gain at fm 16
-    // (profiles/r02_ab_log.md); lv is a flag here, finish.hip compiles the tree depth (PBFT_FIN_LV)
-    int lv = fm <= PBFT_FIN_TREE_MAX_FM ? PBFT_FIN_LV : 0;
-    if (c->fin_m) fm = c->fin_m;
-    if (c->fin_tree >= 0) lv = c->fin_tree;
-    const int fw = c->fin_waves ? c->fin_waves : (big ? PBFT_FIN_W_BIG : 1);
-    LT("finish", HIP_TRY(launch_finish(fm, lv, fw, dR, rs_stride, xyz, flags, N, dB, st)));
+    LT("finish", HIP_TRY(launch_finish_by_n(c, dR, rs_stride, xyz, flags, N, dB, st)));
     HIP_TRY(hipGetLastError());
   }
   if (fst) {
@@ -1951,6 +1958,101 @@ int pbft_verify_batch_device(pbft_ctx* c, const uint8_t* dR, const uint8_t* dS, 
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t st = stream ? (hipStream_t)stream : c->stream;
   return launch_verify(c, dR, dS, dK, dM, msg_len, msg_stride, N, dB, st);
+}
+
+// ---- verification under uninstalled keys (include/pbft_verify.h pbft_verify_batch_keys) ----
+// Two kernel nodes on st: anykey_kernel (anykey.hip: every lane decompresses its own key and computes
+// R' = [s]B + [k](-A) with 4-bit windows), then the finish the one-lane comb has behind it, chosen by N in the same
+// way.  The hand-off lies where the comb's does: xyz and flags of workspace half 0.  No key set is read.
+static int launch_verify_keys(pbft_ctx* c, const uint8_t* dR, const uint8_t* dS, const uint8_t* dA, const uint8_t* dM,
+                              uint32_t msg_len, uint32_t msg_stride, uint64_t N, uint64_t* dB, hipStream_t st) {
+  if (N == 0) return PBFT_OK;
+  if ((N + BLOCK - 1) / BLOCK > 0x7fffffffull) return set_err(PBFT_EINVAL, "N too large for one launch");
+  int rc = ensure_work(c, N);
+  if (rc) return rc;
+  if (c->fin_pending[0]) HIP_TRY(hipStreamWaitEvent(st, c->ev_fin[0], 0));  // a pipelined finish still reading half 0
+  uint32_t* xyz = (uint32_t*)c->d_work;
+  uint8_t* flags = c->d_work + 120 * N;  // within the half's 121 work_n bytes
+  HIP_TRY(launch_anykey(dR, dS, dA, dM, msg_len, msg_stride, N, c->d_tabB, xyz, flags, st));
+  HIP_TRY(launch_finish_by_n(c, dR, 32, xyz, flags, N, dB, st));
+  return PBFT_OK;
+}
+
+int pbft_verify_batch_keys_device(pbft_ctx* c, const uint8_t* dR, const uint8_t* dS, const uint8_t* dA,
+                                  const uint8_t* dM, uint32_t msg_len, uint32_t msg_stride, uint64_t N, uint64_t* dB,
+                                  void* stream) {
+  if (!c) return set_err(PBFT_EINVAL, "null context");
+  if (!check_batch_args(dR, dS, dA, dM, msg_len, msg_stride, N, dB)) return set_err(PBFT_EINVAL, "bad batch arguments");
+  HIP_TRY(hipSetDevice(c->device));
+  return launch_verify_keys(c, dR, dS, dA, dM, msg_len, msg_stride, N, dB, stream ? (hipStream_t)stream : c->stream);
+}
+
+// Device staging of one chunk: R | S | A | msg (+ slack for the message reads past the end)
+struct keys_stage_layout {
+  size_t offS, offA, offM, bytes;
+  keys_stage_layout(uint64_t n, uint32_t msg_stride) {
+    offS = 32 * n;
+    offA = 64 * n;
+    offM = 96 * n;
+    bytes = (offM + (size_t)msg_stride * n + 64 + 255) & ~(size_t)255;
+  }
+};
+
+// Blocking.  Chunks of PIPE_CHUNK signatures, one after the other on the context's stream through one staging buffer
+// (the kernels take several times as long as the copies: nothing to overlap).
+int pbft_verify_batch_keys(pbft_ctx* c, const uint8_t* R, const uint8_t* S, const uint8_t* A, const uint8_t* M,
+                           uint32_t msg_len, uint32_t msg_stride, uint64_t N, uint64_t* out) {
+  if (!c) return set_err(PBFT_EINVAL, "null context");
+  if (c->in_flight) return set_err(PBFT_EBUSY, "async batch in flight");
+  if (!check_batch_args(R, S, A, M, msg_len, msg_stride, N, out)) return set_err(PBFT_EINVAL, "bad batch arguments");
+  if (N == 0) return PBFT_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  const uint64_t words = (N + 63) / 64;
+  const keys_stage_layout L(N < PIPE_CHUNK ? N : PIPE_CHUNK, msg_stride);
+  int rc = ensure_stage(c, L.bytes, words);
+  if (rc) return rc;
+  uint8_t* d = c->d_stage;
+  for (uint64_t lo = 0; lo < N; lo += PIPE_CHUNK) {
+    const uint64_t n = N - lo < PIPE_CHUNK ? N - lo : PIPE_CHUNK;
+    HIP_TRY(hipMemcpyAsync(d, R + 32 * lo, 32 * n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d + L.offS, S + 32 * lo, 32 * n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d + L.offA, A + 32 * lo, 32 * n, hipMemcpyHostToDevice, c->stream));
+    if ((size_t)msg_stride * n)
+      HIP_TRY(hipMemcpyAsync(d + L.offM, M + (size_t)msg_stride * lo, (size_t)msg_stride * n, hipMemcpyHostToDevice,
+                             c->stream));
+    rc = launch_verify_keys(c, d, d + L.offS, d + L.offA, d + L.offM, msg_len, msg_stride, n, c->d_bitmap + lo / 64,
+                            c->stream);
+    if (rc) return rc;
+  }
+  HIP_TRY(hipMemcpyAsync(out, c->d_bitmap, words * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return PBFT_OK;
+}
+
+// Test hook (not declared in include/, like pbft_debug_invert): n triples (s, k, A) of 32 bytes each -> the encoding
+// of [s]B + [k](-A) and the key_ok byte, through anykey_core.h's per-lane sum on the context's base-point table.  The
+// hash is outside it, so a test can place the digits of k (< 2^253).  Host memory; blocking.
+extern "C" int pbft_debug_anykey_point(pbft_ctx* c, const uint8_t* s, const uint8_t* k, const uint8_t* A, uint32_t n,
+                                       uint8_t* enc_out, uint8_t* key_ok_out) {
+  if (!c || !s || !k || !A || !enc_out || !key_ok_out || n == 0 || n > (1u << 20))
+    return set_err(PBFT_EINVAL, "bad arguments");
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t col = (size_t)32 * n;
+  uint8_t* d = nullptr;
+  if (hipMalloc(&d, 4 * col + n) != hipSuccess) return set_err(PBFT_ENOMEM, "point hook alloc");
+  hipError_t e = hipMemcpyAsync(d, s, col, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d + col, k, col, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d + 2 * col, A, col, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess)
+    e = launch_anykey_point((const uint32_t*)d, (const uint32_t*)(d + col), (const uint32_t*)(d + 2 * col), n, c->d_tabB,
+                            (uint32_t*)(d + 3 * col), d + 4 * col, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(enc_out, d + 3 * col, col, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(key_ok_out, d + 4 * col, n, hipMemcpyDeviceToHost, c->stream);
+  const hipError_t es = hipStreamSynchronize(c->stream);
+  (void)hipFree(d);
+  HIP_TRY(e);
+  HIP_TRY(es);
+  return PBFT_OK;
 }
 
 int pbft_verify_batch_device_pipelined(pbft_ctx* c, const uint8_t* dR, const uint8_t* dS, const uint16_t* dK,

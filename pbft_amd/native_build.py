@@ -15,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "pbft_amd", "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
-HIP_SOURCES = ["pbft_verify.hip", "tables.hip", "finish.hip", "sign.hip", "comb_pa13.hip", "comb_pa14.hip", "comb_pa16.hip", "comb_pa32.hip", "tally.hip", "wire_decode.hip", "group.hip", "wire_index.hip", "admit.hip", "wire_pp.hip", "egress.hip", "propose.hip", "reply.hip", "accept.hip", "debug_arith.hip"]
+HIP_SOURCES = ["pbft_verify.hip", "tables.hip", "finish.hip", "sign.hip", "comb_pa13.hip", "comb_pa14.hip", "comb_pa16.hip", "comb_pa32.hip", "tally.hip", "wire_decode.hip", "group.hip", "wire_index.hip", "admit.hip", "wire_pp.hip", "egress.hip", "propose.hip", "reply.hip", "accept.hip", "anykey.hip", "debug_arith.hip"]
 HOST_SOURCES = ["replica.cpp", "wire.cpp"]
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall"]
 HOST_FLAGS = ["-O2", "-std=c++17", "-fPIC", "-Wall", "-Wextra", "-Wno-unknown-pragmas"]

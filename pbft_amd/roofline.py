@@ -68,6 +68,25 @@ def products_per_verify(pb: int, pa: int) -> int:
             + INV_PRODUCTS // ((1 << FIN_TREE_LEVELS) * FIN_M))
 
 
+SQ, MUL = 55, 100  # products of fe_sq / fe_mul
+
+
+def anykey_products(pb: int) -> int:
+    """anykey_kernel alone (anykey_core.h), a key seen for the first time: the second formula.
+      decompression   z^((p-5)/8): 252 squares + 12 multiplies; 4 squares and 11 multiplies round it
+      small order     3 doublings x (4 squares + 4 multiplies)
+      window table    7 additions x 8 multiplies + 8 entry conversions x 1 multiply
+      windows         63 x (3 doublings without T (4 squares + 3 multiplies) + 1 with T (4 + 4)) + 64 additions x 8
+      base point      pb mixed additions x 7 multiplies
+      Barrett         9x9 + 44 word products (k mod L)
+    The finish behind it is the comb's (products_per_verify's last three terms)."""
+    decompress = (252 + 4) * SQ + (12 + 11) * MUL
+    small_order = 3 * (4 * SQ + 4 * MUL)
+    table = 7 * 8 * MUL + 8 * MUL
+    windows = 63 * (3 * (4 * SQ + 3 * MUL) + (4 * SQ + 4 * MUL)) + 64 * 8 * MUL
+    return decompress + small_order + table + windows + pb * 7 * MUL + (81 + 44)
+
+
 def gather_bytes_per_verify(pb: int, pa: int) -> int:
     return (pb + pa) * ENTRY_BYTES
 

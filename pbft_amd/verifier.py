@@ -515,6 +515,42 @@ class GpuBatchVerifier:
         """Pre-size the workspace (required before capturing verify_device into a graph)."""
         check(self._lib.pbft_verify_reserve(self._ctx, max_n))
 
+    # -- uninstalled keys: the public key travels with the signature --------
+    def verify_keys(self, R, S, A, msg, msg_len: int) -> np.ndarray:
+        """pbft_verify_batch_keys: signature i under the key A[i] (32 raw bytes), no key set needed.  Blocking;
+        returns the ceil(N/64) u64 bitmap words."""
+        R = np.ascontiguousarray(R, np.uint8).reshape(-1, 32)
+        S = np.ascontiguousarray(S, np.uint8).reshape(-1, 32)
+        A = np.ascontiguousarray(A, np.uint8).reshape(-1, 32)
+        n = len(R)
+        if len(S) != n or len(A) != n:
+            raise ValueError("R, S and A must have the same length")
+        m = np.ascontiguousarray(msg, np.uint8)
+        if m.ndim == 1:
+            m = m.reshape(n, -1) if n else m.reshape(0, max(msg_len, 1))
+        if m.shape[0] != n or m.shape[1] < msg_len:
+            raise ValueError("msg must be (N, stride >= msg_len)")
+        out = np.zeros((n + 63) // 64, dtype=np.uint64)
+        check(self._lib.pbft_verify_batch_keys(self._ctx, _ptr(R), _ptr(S), _ptr(A), _ptr(m), msg_len, m.shape[1], n,
+                                               _ptr(out)))
+        return out
+
+    def verify_keys_device(self, d_R: int, d_S: int, d_A: int, d_msg: int, msg_len: int, msg_stride: int, n: int,
+                           d_bitmap: int, stream: int = 0) -> None:
+        """pbft_verify_batch_keys_device: enqueue on device-resident buffers (raw device pointers)."""
+        check(self._lib.pbft_verify_batch_keys_device(self._ctx, d_R, d_S, d_A, d_msg, msg_len, msg_stride, n,
+                                                      d_bitmap, stream or None))
+
+    def debug_anykey_point(self, s, k, A):
+        """Test hook: (encodings (n, 32), key_ok (n,)) of [s]B + [k](-A) for n triples of 32-byte rows."""
+        s = np.ascontiguousarray(s, np.uint8).reshape(-1, 32)
+        k = np.ascontiguousarray(k, np.uint8).reshape(-1, 32)
+        A = np.ascontiguousarray(A, np.uint8).reshape(-1, 32)
+        n = len(s)
+        enc, ok = np.zeros((n, 32), np.uint8), np.zeros(n, np.uint8)
+        check(self._lib.pbft_debug_anykey_point(self._ctx, _ptr(s), _ptr(k), _ptr(A), n, _ptr(enc), _ptr(ok)))
+        return enc, ok
+
     def verify_votes(self, R, S, key_idx, env_idx, envelopes) -> np.ndarray:
         """pbft_verify_votes: signature i signs envelopes[env_idx[i]] (85 B each); returns bitmap words."""
         R = np.ascontiguousarray(R, np.uint8).reshape(-1, 32)

@@ -86,7 +86,36 @@ DBL_PRODUCTS = {"A": (C, C), "B": (C, C), "C2": (C, C), "XY2": (DBL_XY, DBL_XY),
                 "X": (C, C), "Y": (C, C), "T": (C, C), "Z": (C, C)}
 
 
+# anykey (anykey_core.h): [k](-A) by 4-bit windows on a key seen for the first time.  Every value that crosses a step
+# boundary is an fe_mul output or an fe_carry output, i.e. within CARRIED, so the three sequences close on themselves:
+#  * doubling chain -> addition -> doubling: ak_dbl takes carried (X, Y, Z) and returns products (DBL_PRODUCTS; its
+#    E', F', G', H' go through fe_carry, whose inputs AK_DBL_CARRY_IN stay below 2^31); ak_add_signed takes the carried
+#    (X, Y, Z, T) of a doubling, of an addition or of the identity and returns products; so does the base-point
+#    ge_madd_signed behind the last addition (MADD_PRODUCTS, as in the comb).
+#  * the projective-Niels addition: D = Z1 * 2Z2 (carried operands) stands where the comb step has Z1, then ge_madd_ab
+#    unchanged: qa, qb are the entry's carried Y2 -+ X2 (the comb's are canonical: the same bound but for the
+#    carry-chain allowance), k' = +-2dT2 of a carried 2dT2 is <= 2p limb-wise like the comb's.
+#  * the entry conversion ak_to_pniels: Y + X, Y - X and 2Z through fe_carry (AK_ENTRY_CARRY_IN), 2dT2 = T * 2d with
+#    the canonical constant.
+AK_DBL_CARRY_IN = {"H'": add(C, C), "E'": sub(C, C, P2), "G'": sub(C, C, P2), "C2": add(C, C), "F'": add(C, C)}
+AK_ENTRY_CARRY_IN = {"Y+X": add(C, C), "Y-X": sub(C, C, P2), "2Z": add(C, C)}
+
+
+def AK_ADD_PRODUCTS(neg):
+    """Operand bounds of the eight products of ak_add_signed: D, then ge_madd_ab's seven on (X, Y, D, T)."""
+    return {"D": (C, C), **MADD_PRODUCTS(neg)}
+
+
+AK_ENTRY_PRODUCT = (C, TABLE)  # T * 2d
+
+
 def main():
+    for nm, v in {**AK_DBL_CARRY_IN, **AK_ENTRY_CARRY_IN}.items():
+        assert max(v) < 2**31, nm  # fe_carry's precondition
+    for neg in (False, True):
+        for nm, (x, y) in AK_ADD_PRODUCTS(neg).items():  # (mulmax asserts each operand's role: 2x odd limbs, 19x)
+            print("anykey add neg=%d %-3s log2 max col:" % (neg, nm), mulmax(x, y))
+    print("anykey entry 2dT    log2 max col:", mulmax(*AK_ENTRY_PRODUCT))
     # mixed add (comb step): P3 + halved affine Niels ((y+x)/2, (y-x)/2, dxy) with canonical table limbs
     print("madd a=(Y-X)*ymx   log2 max col:", mulmax(YMX, C))
     print("madd b=(Y+X)*ypx   log2 max col:", mulmax(YPX, C))
